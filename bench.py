@@ -9,18 +9,28 @@ value = B * world / step_time  (adversarial text samples/s; the reference's own 
     python bench.py --gpus 2 --steps 50           # starts 2 ranks itself (torch.distributed.run, RCCL)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W    # the driver's form: runs as launched
+    python bench.py --full                        # + roofline, dense and fast-arithmetic legs, CPU baseline, parity
+    python bench.py --dump-outputs DIR            # + DIR/<name>.npy: what the last timed step computed
 
-Prints ONE JSON line on rank 0: the task contract's fields, plus
-  roofline      the dominant GEMM kernel, timed live with HIP events around every launch on its own stream
-                (leaf_prof_*), and `shapes`: the same figures per GEMM shape (N, K) of every kernel family;
-  cpu_baseline  a plain PyTorch-CPU fp32 harness of the same step (oracle/torch_cpu_harness.py) on BASELINE.json
-                configs[0] (B = 8), bounded in time, all usable host cores (rank 0, N = 1 only);
-  dense         samples/s of the same step with every exact work-skipping switched off (a few steps, after the timed region);
-  step_exec_frac    executed GEMM FLOP/s of the whole step / dense 16-bit MFMA peak  (the honest step-level fraction);
+A plain run sets up, warms up, times --steps steps and prints ONE JSON line on rank 0: the task contract's fields, plus
   dense_equiv_frac  samples/s x dense algorithmic FLOPs per sample / peak (SURVEY.md 8d's prescription; exceeds the
                     executed fraction by the factor exact work skipping removes);
   ms_per_step_first_tenth / _last_tenth   the step is data dependent (the rows the second stage computes follow the search's
                     winners, which move as the model trains on the synthetic batch): both ends of the timed region.
+--full adds what takes work of its own beside the headline:
+  roofline      the dominant GEMM kernel, timed live with HIP events around every launch on its own stream
+                (leaf_prof_*, on every --prof-every-th timed step), and `shapes`: the same figures per GEMM shape (N, K) of every
+                kernel family; with it step_exec_frac (executed GEMM FLOP/s of the whole step / dense 16-bit MFMA peak: the honest
+                step-level fraction) and the HBM traffic of a matching PMC summary under profiles/;
+  dense         samples/s of the same step with every exact work-skipping switched off (a few steps, after the timed region);
+  fast_arithmetic   samples/s of the same step without the split GEMMs (after the timed region);
+  cpu_baseline  a plain PyTorch-CPU fp32 harness of the same step (oracle/torch_cpu_harness.py) on BASELINE.json
+                configs[0] (B = 8), bounded in time, all usable host cores (rank 0, N = 1 only), and parity_rel_l2: the
+                benchmark model's embeddings against that harness's fp32 forward.
+--dump-outputs DIR writes, right after the timed steps and before anything --full adds, what the timed path handed its caller
+in its last step (rank 0): the TextFARE loss and a fixed, seeded sample of the model it updated in place (dump_outputs()).
+The inputs depend on the arguments only (seeded batches and candidates) and the step sums in a fixed order, so two runs with
+the same arguments write the same bits and two builds can be compared output for output.
 """
 import argparse
 import ctypes as C
@@ -104,6 +114,29 @@ def cpu_baseline(model_name, rho, k, b_cpu, seed, budget_s, gpu_encode=None, par
                        f"({r['t_train_s']:.1f} s); {r['wall_s']:.1f} s of CPU time spent")}
 
 
+DUMP_SAMPLE = 1 << 21       # positions per flat-buffer sample of --dump-outputs: 8 MiB per array in fp32, 24 MiB in all
+
+
+def dump_outputs(out_dir, model, loss):
+    """--dump-outputs DIR: what train_step_tokens handed its caller after the LAST timed step -- the TextFARE loss it returned
+    (``loss.npy``, [1]) and the model it updated in place: fp32 master weights after the AdamW step (``weights.npy``), the step's
+    gradient (``grads.npy``) and AdamW's first moment (``exp_avg.npy``).  The three flat buffers are sampled at the same fixed
+    positions (DUMP_SAMPLE draws seeded by 0, sorted, duplicates removed; every position when the model is smaller).  float32."""
+    import numpy as np
+    import torch
+    n = model.n_params
+    if n > DUMP_SAMPLE:
+        idx = torch.randint(0, n, (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(0), dtype=torch.int64).unique()
+    else:
+        idx = torch.arange(n, dtype=torch.int64)
+    idx = idx.to(model.flat.device)
+    arrays = {"loss": loss.detach().float().reshape(1), "weights": model.flat[idx], "grads": model.grads[idx],
+              "exp_avg": model.exp_avg[idx]}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.cpu().numpy().astype(np.float32))
+
+
 def free_port():
     with socket.socket() as s:
         s.bind(("127.0.0.1", 0))
@@ -122,6 +155,89 @@ def step_trend(marks):
     last = marks[n - 1 - k].elapsed_time(marks[n - 1]) / k
     return {"ms_per_step_first_tenth": first, "ms_per_step_last_tenth": last,
             "step_time_note": "data dependent (exact work skipping follows the search's winners as the model trains); value = all timed steps"}
+
+
+def live_roofline(lib, sampled_steps, steps, dt, wkey):
+    """--full: the per-launch HIP events of the sampled timed steps (leaf_prof_*) -> the line's `roofline` (the dominant GEMM
+    kernel and every (kernel, N, K) shape), the executed GEMM figures of the whole step and, where profiles/ holds a PMC summary
+    of the same kernel sources and workload, the dominant kernel's measured HBM bytes per launch."""
+    from leaf_amd import _lib
+    ng = 256
+    ms, fl, by = (C.c_double * ng)(), (C.c_double * ng)(), (C.c_double * ng)()
+    rows, info, n_out = (C.c_int64 * ng)(), (C.c_int32 * (4 * ng))(), C.c_int(0)
+    _lib.check(lib.leaf_prof_end_shapes(ms, fl, by, rows, info, ng, C.byref(n_out)), "leaf_prof_end_shapes")
+    shapes, per_key = [], {}
+    psteps = max(sampled_steps, 1)          # timed steps whose launches carry events
+    for i in range(n_out.value):
+        key, N, K, cnt = info[4 * i], info[4 * i + 1], info[4 * i + 2], info[4 * i + 3]
+        big, key = key >= 1024, key % 1024        # launches of >= 16,384 rows (the scoring passes) are grouped apart
+        if ms[i] <= 0:
+            continue
+        kname = f"{FAMILY.get(key // 32, 'gemm?')}<{'F16' if (key // 16) % 2 == 1 else 'BF16'},{key % 16}>"
+        tf = fl[i] / (ms[i] * 1e-3) / 1e12
+        gbs = by[i] / (ms[i] * 1e-3) / 1e9
+        # which roofline bounds this shape: algorithmic FLOP per algorithmic byte against the machine balance
+        intensity = fl[i] / by[i]
+        bound = "hbm" if intensity < PEAK_TFLOPS_16BIT * 1e12 / (PEAK_HBM_GBS * 1e9) * 0.5 else "mfma"
+        shapes.append({"kernel": kname, "epilogue": EPI_NAMES.get(key % 16), "N": N, "K": K, "launches": cnt, "big_launches": big,
+                       "rows_per_launch": rows[i] / cnt, "ms_per_step": ms[i] / psteps, "tflops": tf,
+                       "mfma_frac": tf / PEAK_TFLOPS_16BIT, "algorithmic_gbs": gbs, "hbm_frac": gbs / PEAK_HBM_GBS,
+                       "flop_per_byte": intensity, "bound": bound, "algorithmic_bytes_per_launch": by[i] / cnt})
+        a = per_key.setdefault(key, [0.0, 0.0, 0.0, 0])
+        a[0] += ms[i]; a[1] += fl[i]; a[2] += by[i]; a[3] += cnt
+    shapes.sort(key=lambda s: -s["ms_per_step"])
+    dom_key = max(per_key, key=lambda k: per_key[k][0])
+    dom_ms, dom_fl, dom_bytes, dom_cnt = per_key[dom_key]
+    dom_name = f"{FAMILY.get(dom_key // 32, 'gemm?')}<{'F16' if (dom_key // 16) % 2 == 1 else 'BF16'},{dom_key % 16}>"
+    achieved = dom_fl / (dom_ms * 1e-3) / 1e12
+    gemm_total_ms = sum(v[0] for v in per_key.values())
+    gemm_total_fl = sum(v[1] for v in per_key.values())
+    traffic, traffic_note, traffic_kernels = None, "no PMC summary under profiles/ for this kernel build and workload", None
+    default_key = "ViT-L-14-quickgelu|B128|accum1|k1|rho50|leaf|trimmed|prefix|freshbatch"
+    try:    # HBM bytes per launch of the dominant kernel from the committed PMC passes; only for the build AND workload they were taken on
+        import glob
+        stale = False
+        for path in sorted(glob.glob(os.path.join(ROOT, "profiles", TRAFFIC_GLOB))):
+            with open(path) as f:
+                tj = json.load(f)
+            if tj.get("workload_key", default_key) != wkey:
+                continue
+            name = "profiles/" + os.path.basename(path)
+            if tj.get("kernel_sources_sha16") != kernel_sources_hash():
+                stale = True
+                traffic_note = name + " was taken on different kernel sources: not attached"
+                continue
+            traffic_kernels = tj.get("kernels")        # every big kernel: measured bytes / algorithmic bytes of the PMC run itself
+            if tj.get("kernel") == dom_name:
+                traffic = tj["traffic_bytes_per_launch"]
+                traffic_note = ("HBM bytes per launch, rocprofv3 PMC (2*FETCH_SIZE + WRITE_SIZE) * 1024, separate passes, "
+                                + name + " (same kernel sources, sha16 " + tj["kernel_sources_sha16"] + ", same workload; that run's own "
+                                f"algorithmic bytes per launch: {tj.get('algorithmic_bytes_per_launch')})")
+            else:
+                traffic_note = name + " names " + str(tj.get("kernel")) + " as dominant, this line " + dom_name + ": per-kernel list attached only"
+            break
+        else:
+            if not stale:
+                traffic_note = ("no PMC summary under profiles/ for this workload (" + wkey + "): tools/pmc_passes.sh + "
+                                "tools/pmc_summary.py produce it")
+    except (OSError, ValueError, KeyError):
+        pass
+    return {
+        "roofline": {
+            "bound": "mfma", "achieved": achieved, "peak": PEAK_TFLOPS_16BIT, "unit": "TFLOP/s",
+            "frac": achieved / PEAK_TFLOPS_16BIT, "traffic": traffic, "traffic_note": traffic_note, "traffic_kernels": traffic_kernels,
+            "kernel": f"{dom_name} {EPI_NAMES.get(dom_key % 16)}",
+            "algorithmic_bytes_per_launch": dom_bytes / dom_cnt if dom_bytes else None,
+            "launches": int(dom_cnt), "avg_launch_ms": dom_ms / dom_cnt,
+            "algorithmic_gflop_per_launch": dom_fl / dom_cnt / 1e9,
+            "all_gemm_tflops": gemm_total_fl / (gemm_total_ms * 1e-3) / 1e12,
+            "gemm_share_of_step": gemm_total_ms * 1e-3 / (dt * psteps / steps),
+            "sampled_steps": psteps,
+            "shapes": shapes[:16],
+        },
+        "step_exec_frac": gemm_total_fl / (dt * psteps / steps) / (PEAK_TFLOPS_16BIT * 1e12),
+        "executed_gemm_tflop_per_step": gemm_total_fl / psteps / 1e12,
+    }
 
 
 def self_launch(args, argv):
@@ -323,8 +439,14 @@ def main():
     ap.add_argument("--k-adv", type=int, default=int(os.environ.get("LEAF_BENCH_K", "1")))
     ap.add_argument("--accum-freq", type=int, default=1, help="micro-batches per optimizer step (configs[3]: --batch 32 --accum-freq 4)")
     ap.add_argument("--dtype", default=os.environ.get("LEAF_DTYPE", "fp16"), choices=["fp16", "bf16"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-dense-leg", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: the live per-shape GEMM roofline (per-launch events inside the "
+                         "timed region), the dense and fast-arithmetic legs, the PyTorch-CPU baseline and the parity rows")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed to DIR/<name>.npy (loss, sampled weights / "
+                         "gradient / AdamW moment; rank 0)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the PyTorch-CPU baseline and the parity rows")
+    ap.add_argument("--no-dense-leg", action="store_true", help="(--full) skip the dense and fast-arithmetic legs")
     ap.add_argument("--dense", action="store_true", help="compute all 77 rows per sequence (no EOT trimming)")
     ap.add_argument("--no-prefix-reuse", action="store_true", help="recompute every kept row of every candidate")
     ap.add_argument("--cpu-batch", type=int, default=8)
@@ -334,7 +456,7 @@ def main():
                     help="host threads per rank (torch CPU ops, the native tokenizer: LEAF_HOST_THREADS); default = usable cores // ranks on this node")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"])
     ap.add_argument("--prof-every", type=int, default=4,
-                    help="take the per-launch HIP events of the live roofline on every N-th timed step (an event pair makes the queue wait for the "
+                    help="(--full) take the per-launch HIP events of the live roofline on every N-th timed step (an event pair makes the queue wait for the "
                          "launch before it: 1.2 ms per 50-ms step when taken on all of them)")
     ap.add_argument("--dry", action="store_true", help="rendezvous rehearsal only (no GPU work); with --backend gloo runs on CPU")
     ap.add_argument("--precision", default=None, choices=["rowsafe", "fast"],
@@ -371,6 +493,10 @@ def main():
                     help="BASELINE.json configs[i] verbatim (model, k, per-GPU batch, accum): 1 = ViT-L k=1 B=128 (the default), "
                          "2 = ViT-L k=5 B=128, 3 = ViT-H k=2 B=128 as accum 4 x 32, 4 = ViT-bigG k=1 B=256; explicit flags still win")
     args = ap.parse_args()
+    if args.dump_outputs and (args.dry or args.rank_sim):
+        ap.error("--dump-outputs writes the metric's step: not with --dry or --rank-sim")
+    if (args.no_cpu_baseline or args.no_dense_leg) and not args.full:
+        print("bench.py: --no-cpu-baseline / --no-dense-leg only trim a --full run; a plain run has neither leg", file=sys.stderr)
     if args.config:
         preset = {1: dict(model="ViT-L-14-quickgelu", k_adv=1, batch=128, accum_freq=1),
                   2: dict(model="ViT-L-14-quickgelu", k_adv=5, batch=128, accum_freq=1),
@@ -531,7 +657,8 @@ def main():
     reducer.exposed_ms()          # drop the warm-up's pairs
     rows0 = model.rows_scored
     barrier()
-    if rank == 0 and os.environ.get("LEAF_BENCH_NO_PROF") != "1":     # (=1: overhead probe of the live per-launch events; the line then has no roofline)
+    # the live roofline (--full only): (LEAF_BENCH_NO_PROF=1: overhead probe of the live per-launch events; the line then has no roofline)
+    if args.full and rank == 0 and os.environ.get("LEAF_BENCH_NO_PROF") != "1":
         lib.leaf_prof_begin()
         prof["on"] = True
     t0 = time.perf_counter()
@@ -539,6 +666,8 @@ def main():
     prof["on"] = False
     barrier()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, model, loss)
     tmax = torch.tensor([dt], dtype=torch.float64, device=dev)
     gathered = None
     if use_dist:
@@ -559,75 +688,16 @@ def main():
         return
 
     if rank == 0:
-        ng = 256
-        ms, fl, by = (C.c_double * ng)(), (C.c_double * ng)(), (C.c_double * ng)()
-        rows, info, n_out = (C.c_int64 * ng)(), (C.c_int32 * (4 * ng))(), C.c_int(0)
-        _lib.check(lib.leaf_prof_end_shapes(ms, fl, by, rows, info, ng, C.byref(n_out)), "leaf_prof_end_shapes")
-        shapes, per_key = [], {}
-        psteps = max(prof["steps"], 1)          # timed steps whose launches carry events
-        for i in range(n_out.value):
-            key, N, K, cnt = info[4 * i], info[4 * i + 1], info[4 * i + 2], info[4 * i + 3]
-            big, key = key >= 1024, key % 1024        # launches of >= 16,384 rows (the scoring passes) are grouped apart
-            if ms[i] <= 0:
-                continue
-            kname = f"{FAMILY.get(key // 32, 'gemm?')}<{'F16' if (key // 16) % 2 == 1 else 'BF16'},{key % 16}>"
-            tf = fl[i] / (ms[i] * 1e-3) / 1e12
-            gbs = by[i] / (ms[i] * 1e-3) / 1e9
-            # which roofline bounds this shape: algorithmic FLOP per algorithmic byte against the machine balance
-            intensity = fl[i] / by[i]
-            bound = "hbm" if intensity < PEAK_TFLOPS_16BIT * 1e12 / (PEAK_HBM_GBS * 1e9) * 0.5 else "mfma"
-            shapes.append({"kernel": kname, "epilogue": EPI_NAMES.get(key % 16), "N": N, "K": K, "launches": cnt, "big_launches": big,
-                           "rows_per_launch": rows[i] / cnt, "ms_per_step": ms[i] / psteps, "tflops": tf,
-                           "mfma_frac": tf / PEAK_TFLOPS_16BIT, "algorithmic_gbs": gbs, "hbm_frac": gbs / PEAK_HBM_GBS,
-                           "flop_per_byte": intensity, "bound": bound, "algorithmic_bytes_per_launch": by[i] / cnt})
-            a = per_key.setdefault(key, [0.0, 0.0, 0.0, 0])
-            a[0] += ms[i]; a[1] += fl[i]; a[2] += by[i]; a[3] += cnt
-        shapes.sort(key=lambda s: -s["ms_per_step"])
-        dom_key = max(per_key, key=lambda k: per_key[k][0])
-        dom_ms, dom_fl, dom_bytes, dom_cnt = per_key[dom_key]
-        dom_name = f"{FAMILY.get(dom_key // 32, 'gemm?')}<{'F16' if (dom_key // 16) % 2 == 1 else 'BF16'},{dom_key % 16}>"
-        achieved = dom_fl / (dom_ms * 1e-3) / 1e12
-        gemm_total_ms = sum(v[0] for v in per_key.values())
-        gemm_total_fl = sum(v[1] for v in per_key.values())
         F = fwd_flops_per_seq(cfg)
         # algorithmic cost per sample: LEAF search (2 rho k candidate forwards + anchor + train fwd + 2x bwd), or for the
         # optional embedding-space PGD mode k x (fwd + input-gradient bwd ~ 1 + 1) on top of anchor + start fwd + train bwd
         flops_per_sample = (2 * args.rho * args.k_adv + 4) * F if args.attack == "leaf" else (2 * args.k_adv + 4) * F
         value = B * world * args.steps / dt
-        traffic, traffic_note, traffic_kernels = None, "no PMC summary under profiles/ for this kernel build and workload", None
         # workload a PMC summary belongs to: tools/pmc_summary.py copies this key from the line of its own FETCH pass
         wkey = (f"{args.model}|B{B}|accum{args.accum_freq}|k{args.k_adv}|rho{args.rho}|{args.attack}|"
                 f"{'dense' if args.dense else 'trimmed'}|{'noprefix' if args.no_prefix_reuse else 'prefix'}|{'fixedbatch' if args.fixed_batch else 'freshbatch'}"
                 + ("" if arith == "rowsafe" else "|" + arith) + ("" if compact else "|fp32resid") + ("|preciseanchor" if args.precise_anchor else ""))
-        default_key = "ViT-L-14-quickgelu|B128|accum1|k1|rho50|leaf|trimmed|prefix|freshbatch"
-        try:    # HBM bytes per launch of the dominant kernel from the committed PMC passes; only for the build AND workload they were taken on
-            import glob
-            stale = False
-            for path in sorted(glob.glob(os.path.join(ROOT, "profiles", TRAFFIC_GLOB))):
-                with open(path) as f:
-                    tj = json.load(f)
-                if tj.get("workload_key", default_key) != wkey:
-                    continue
-                name = "profiles/" + os.path.basename(path)
-                if tj.get("kernel_sources_sha16") != kernel_sources_hash():
-                    stale = True
-                    traffic_note = name + " was taken on different kernel sources: not attached"
-                    continue
-                traffic_kernels = tj.get("kernels")        # every big kernel: measured bytes / algorithmic bytes of the PMC run itself
-                if tj.get("kernel") == dom_name:
-                    traffic = tj["traffic_bytes_per_launch"]
-                    traffic_note = ("HBM bytes per launch, rocprofv3 PMC (2*FETCH_SIZE + WRITE_SIZE) * 1024, separate passes, "
-                                    + name + " (same kernel sources, sha16 " + tj["kernel_sources_sha16"] + ", same workload; that run's own "
-                                    f"algorithmic bytes per launch: {tj.get('algorithmic_bytes_per_launch')})")
-                else:
-                    traffic_note = name + " names " + str(tj.get("kernel")) + " as dominant, this line " + dom_name + ": per-kernel list attached only"
-                break
-            else:
-                if not stale:
-                    traffic_note = ("no PMC summary under profiles/ for this workload (" + wkey + "): tools/pmc_passes.sh + "
-                                    "tools/pmc_summary.py produce it")
-        except (OSError, ValueError, KeyError):
-            pass
+        full_fields = live_roofline(lib, prof["steps"], args.steps, dt, wkey) if prof["steps"] else {}   # --full only
         out = {
             "metric": "adversarial text samples/sec", "value": value, "unit": "samples/s",
             "n_gpus": world, "n_ranks_seen": n_ranks_seen, "steps": args.steps, "warmup": args.warmup,
@@ -652,19 +722,7 @@ def main():
                                            if compact else "fp32"), "accum_freq": args.accum_freq, "baseline_config_index": args.config or None, "workload_key": wkey,
                        "global_batch": B * world, "seq_len": cfg.context_length, "rho": args.rho, "k": args.k_adv,
                        "parallelism": f"dp{world}", "candidate_forwards_per_step_per_gpu": 2 * args.rho * args.k_adv * B},
-            "roofline": {
-                "bound": "mfma", "achieved": achieved, "peak": PEAK_TFLOPS_16BIT, "unit": "TFLOP/s",
-                "frac": achieved / PEAK_TFLOPS_16BIT, "traffic": traffic, "traffic_note": traffic_note, "traffic_kernels": traffic_kernels,
-                "kernel": f"{dom_name} {EPI_NAMES.get(dom_key % 16)}",
-                "algorithmic_bytes_per_launch": dom_bytes / dom_cnt if dom_bytes else None,
-                "launches": int(dom_cnt), "avg_launch_ms": dom_ms / dom_cnt,
-                "algorithmic_gflop_per_launch": dom_fl / dom_cnt / 1e9,
-                "all_gemm_tflops": gemm_total_fl / (gemm_total_ms * 1e-3) / 1e12,
-                "gemm_share_of_step": gemm_total_ms * 1e-3 / (dt * psteps / args.steps),
-                "sampled_steps": psteps,
-                "shapes": shapes[:16],
-            },
-            "step_exec_frac": gemm_total_fl / (dt * psteps / args.steps) / (PEAK_TFLOPS_16BIT * 1e12),
+            **full_fields,
             **step_trend(step_marks),
             "dense_equiv_frac": value * flops_per_sample / (world * PEAK_TFLOPS_16BIT * 1e12),
             "algorithmic_tflop_per_sample": flops_per_sample / 1e12,
@@ -673,12 +731,12 @@ def main():
                                    f"mean kept rows {sum(lens_seen) / len(lens_seen):.1f} of 77" +
                                    ("" if args.no_prefix_reuse else "; prefix reuse: rows before the edited token come "
                                     "from the clean caption's per-layer K/V cache (bit-identical outputs)"),
-            "executed_gemm_tflop_per_step": gemm_total_fl / psteps / 1e12,
             "kernel_sources_sha16": kernel_sources_hash(),
             "loss": float(loss),
         }
+    # ---- --full from here on: legs of their own after the timed region, the CPU baseline and the parity rows
     # ---- dense leg: the same step with every exact work-skipping switched off (outside the timed region, all ranks)
-    if not args.no_dense_leg and not args.dense and args.attack == "leaf" and world == 1:
+    if args.full and not args.no_dense_leg and not args.dense and args.attack == "leaf" and world == 1:
         n_dense = 3
         run_steps(1, None, False)
         torch.cuda.synchronize()
@@ -691,7 +749,7 @@ def main():
                             "note": "every sequence 77 rows, no prefix reuse (the reference's own amount of arithmetic)"}
     # ---- fast-arithmetic leg: the same step without the split GEMMs (the rounds 1-5 arithmetic), same box, outside the timed region --
     # what the default's per-row parity costs, readable from one line
-    if not args.no_dense_leg and not args.dense and args.attack == "leaf" and world == 1 and model.split_masks:
+    if args.full and not args.no_dense_leg and not args.dense and args.attack == "leaf" and world == 1 and model.split_masks:
         keep = model.split_masks
         model.set_precision("fast")
         frozen.set_precision("fast")          # (arithmetic only: the frozen model keeps its start weights -- the parity check below reads them)
@@ -709,7 +767,7 @@ def main():
                                       "note": "no split GEMMs (--precision fast; weights as trained so far): batch rel-L2 8.7e-4 but 1.1 % of the "
                                               "embedding rows above 1e-3 (profiles/r06_row_error_census.txt); NOT the metric"}
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline and args.attack == "leaf":
+        if args.full and world == 1 and not args.no_cpu_baseline and args.attack == "leaf":
             oracle_name = args.model if args.model in ("ViT-L-14", "ViT-L-14-quickgelu", "ViT-H-14", "ViT-g-14", "ViT-bigG-14") else "ViT-L-14"
             same_weights = oracle_name == args.model          # the frozen model still holds the seed-1 start weights
             out["cpu_baseline"] = cpu_baseline(oracle_name, args.rho, args.k_adv, args.cpu_batch, seed=1234, budget_s=args.cpu_budget_s,

@@ -212,7 +212,7 @@ static int backward_impl(leaf_text_t h, const float* P, const void* w16_bwd, con
             const void* bufs[5] = {b.dx16, b.big16, b.dx16b, b.do16, b.dqkv};
             const size_t numel[5] = {rd, 4 * rd, rd, rd, 3 * rd};
             // poison target: the first element of the token-embedding gradient.  Everything that still touches it after this
-            // launch only ADDS to it (the embedding scatter's atomics: NaN stays NaN), and it travels in the LAST bucket of the
+            // launch only ADDS to it (the embedding scatter adds into it: NaN stays NaN), and it travels in the LAST bucket of the
             // data-parallel reduction (step.bucket_plan: offset 0, behind the last block's event), so no rank can ship a clean
             // element 0 before another rank's poison exists (tests/test_dp_gloo.py pins both facts)
             LEAF_TRY(leaf_launch_sat_check16(bufs, numel, 5, h->scaler, G + h->tok_emb, s));

@@ -433,7 +433,7 @@ __global__ __launch_bounds__(256) void ln_param_reduce_kernel(LnReduceArgs a) {
     }
 }
 
-// dpos[p][:] += sum_n dx[n*ctx+p][:]   (grid = ctx) ; dtok via atomics (grid-stride over rows)
+// dpos[p][:] += sum_n dx[n*ctx+p][:]   (grid = ctx) ; dtok: tok_bwd_kernel below
 __global__ __launch_bounds__(256) void pos_bwd_kernel(const float* __restrict__ dx, const float* __restrict__ gscale,
                                                       float* __restrict__ dpos, int n_seq, RowMap map, int d) {
     leaf_fp16_sat_mode();
@@ -456,16 +456,66 @@ __global__ __launch_bounds__(256) void pos_bwd_kernel(const float* __restrict__ 
         dpos[(size_t)p * d + c] += s * gscale[1];
     }
 }
+// dtok[tok][:] += dx[row][:] * inv for every row, summed in ROW order so that a step gives the same bits on every run (one float
+// atomic per row summed the rows of a repeated id -- SOT, EOT, pads, repeated words -- in whatever order the blocks ran).  One block
+// per row; the launch's token slots are scanned flat, slot j = (sequence s0 + j / ctx, position j % ctx), valid while the position
+// is inside the sequence's rows, so slot order is row order.  A block whose id occurs in an earlier row returns; the block of the
+// id's FIRST row is the only writer of dtok[tok] and adds all of the id's rows in row order, 256 slots per window.
+__device__ __forceinline__ int tok_clamp(int t, int vocab) { return t < 0 ? 0 : (t >= vocab ? vocab - 1 : t); }
 __global__ __launch_bounds__(256) void tok_bwd_kernel(const float* __restrict__ dx, const float* __restrict__ gscale,
                                                       const int32_t* __restrict__ tokens, float* __restrict__ dtok, int rows,
                                                       int n_seq, RowMap map, int d, int vocab) {
     leaf_fp16_sat_mode();
+    __shared__ int list[256];
+    __shared__ int wcnt[4];
     const int row = blockIdx.x;
     const int sq = seq_of_row(map, row, n_seq);
-    int tok = tokens[(size_t)sq * map.ctx + (row - seq_row(map, sq))];
-    tok = tok < 0 ? 0 : (tok >= vocab ? vocab - 1 : tok);
+    const int pos = row - seq_row(map, sq);
+    const int tok = tok_clamp(tokens[(size_t)sq * map.ctx + pos], vocab);
+    const int32_t* tk = tokens + (size_t)map.s0 * map.ctx;
+    const int me = (sq - map.s0) * map.ctx + pos, end = n_seq * map.ctx;
+    // 1. one pass over all slots: does the id occur in an earlier row (that row's block owns dtok[tok]) or in a later one?
+    bool earlier = false, later = false;
+#pragma unroll 4
+    for (int j = threadIdx.x; j < end; j += 256) {
+        // the id first (one coalesced load); the slot's position inside its sequence only for the rare slots that match
+        const bool hit = tok_clamp(tk[j], vocab) == tok && j % map.ctx < seq_len(map, map.s0 + j / map.ctx);
+        earlier |= hit && j < me;
+        later |= hit && j > me;
+    }
+    if (__syncthreads_or(earlier)) return;
     const float inv = gscale[1];
-    for (int c = threadIdx.x; c < d; c += 256) atomicAdd(dtok + (size_t)tok * d + c, dx[(size_t)row * d + c] * inv);
+    float* dst = dtok + (size_t)tok * d;
+    if (!__syncthreads_or(later)) {         // the id's only row (most rows): no ordering to keep
+        for (int c = threadIdx.x; c < d; c += 256) dst[c] += dx[(size_t)row * d + c] * inv;
+        return;
+    }
+    // 2. this block owns a repeated id: its rows from this one on, in row order
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    for (int w = me; w < end; w += 256) {
+        const int j = w + threadIdx.x;
+        int r = -1;
+        if (j < end) {
+            const int s = map.s0 + j / map.ctx, q = j % map.ctx;
+            if (tok_clamp(tk[j], vocab) == tok && q < seq_len(map, s)) r = seq_row(map, s) + q;
+            if (r >= rows) r = -1;          // (the launch's rows are the sequences' rows; never read past dx)
+        }
+        if (__syncthreads_count(r >= 0) == 0) continue;
+        const unsigned long long bal = __ballot(r >= 0);
+        if (lane == 0) wcnt[wv] = __popcll(bal);
+        __syncthreads();
+        int base = 0, total = 0;
+        for (int k = 0; k < 4; ++k) { base += k < wv ? wcnt[k] : 0; total += wcnt[k]; }
+        if (r >= 0) list[base + __popcll(bal & ((1ull << lane) - 1))] = r;
+        __syncthreads();
+        for (int c = threadIdx.x; c < d; c += 256) {
+            float acc = dst[c];
+#pragma unroll 8
+            for (int i = 0; i < total; ++i) acc += dx[(size_t)list[i] * d + c] * inv;     // loads in flight, adds in row order
+            dst[c] = acc;
+        }
+        __syncthreads();            // list / wcnt are rewritten by the next window
+    }
 }
 
 __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const float* __restrict__ g,

@@ -178,6 +178,71 @@ def test_bench_fresh_batches_fixed_batch_and_rank_sim():
     assert sim["scored_rows_per_rank_step_min_mean_max"][0] > 0
 
 
+def test_bench_plain_line_full_legs_and_dumped_outputs(tmp_path):
+    """A plain bench run times --steps steps and prints the headline only; --full adds the live roofline and the legs after the
+    timed region; --dump-outputs DIR writes what the last timed step computed (the loss and fixed samples of the weights, the
+    gradient and AdamW's first moment, float32), the same outputs for the same arguments, and before anything --full adds."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    common = ["--model", "tiny-test-quickgelu", "--batch", "16", "--rho", "8", "--steps", "5", "--warmup", "2"]
+
+    def run(extra):
+        p = subprocess.run([sys.executable, os.path.join(root, "bench.py")] + common + extra, env=env, capture_output=True, text=True,
+                           timeout=600, cwd=root)
+        assert p.returncode == 0, p.stderr[-3000:]
+        line = [l for l in p.stdout.splitlines() if l.startswith("{")]
+        assert len(line) == 1, p.stdout[-2000:]
+        return json.loads(line[0])
+    plain = run(["--dump-outputs", str(tmp_path / "a")])
+    again = run(["--dump-outputs", str(tmp_path / "b")])
+    full = run(["--full", "--no-cpu-baseline", "--dump-outputs", str(tmp_path / "c")])
+    for d in (plain, full):
+        assert d["metric"] == "adversarial text samples/sec" and d["unit"] == "samples/s" and d["higher_is_better"] is True
+        assert d["steps"] == 5 and abs(d["value"] - 16 * 5 / (d["ms_per_step"] * 5e-3)) < 1e-6 * d["value"] and "fp16" in d["dtype"]
+    assert not {"roofline", "step_exec_frac", "dense", "fast_arithmetic", "cpu_baseline", "parity_rel_l2"} & set(plain)
+    assert {"roofline", "step_exec_frac", "dense"} <= set(full) and full["roofline"]["sampled_steps"] >= 1
+    assert ("fast_arithmetic" in full) == bool(full["config"]["split_masks"])
+    names = ("loss", "weights", "grads", "exp_avg")
+    assert sorted(os.listdir(tmp_path / "a")) == sorted(n + ".npy" for n in names)
+    assert sum(os.path.getsize(tmp_path / "a" / (n + ".npy")) for n in names) < 64 << 20
+    a, b, c = ({n: np.load(tmp_path / x / (n + ".npy")) for n in names} for x in "abc")
+    assert a["loss"].shape == (1,) and float(a["loss"][0]) == np.float32(plain["loss"])
+    assert a["weights"].shape == a["grads"].shape == a["exp_avg"].shape and a["weights"].size > 1000
+    for n in names:                   # same arguments, same bits: --full only adds events around the same launches
+        assert a[n].dtype == np.float32 and np.isfinite(a[n]).all()
+        assert np.array_equal(a[n], b[n]) and np.array_equal(a[n], c[n]), n
+    assert np.any(a["grads"] != 0)
+
+
+def test_backward_is_bitwise_repeatable_with_repeated_token_ids():
+    """The embedding-table gradient adds the rows of a repeated id (SOT and EOT in every caption, the pad id in the dense layout)
+    in row order, one block per id (tok_bwd_kernel): three backward passes of one 128-caption batch give the same bits, packed
+    and dense."""
+    import torch
+    from leaf_amd.model import LeafCLIPText, create_model, get_config
+    m = create_model("tiny-test-quickgelu", seed=3, trainable=True)
+    frozen = LeafCLIPText(get_config("tiny-test-quickgelu")).copy_from(m)
+    base = torch.from_numpy(O.synthetic_tokens(128, seed=7).astype(np.int32)).cuda()
+    lens = (base.argmax(-1) + 1).cpu().numpy().astype(np.int32)
+    anchor = frozen.encode_text(base)
+    off, shape = m.layout["token_embedding.weight"]
+    for seq_lens in (lens, None):
+        got = []
+        for _ in range(3):
+            feat = m.forward_train(base, seq_lens=seq_lens)
+            m.zero_grad()
+            m.backward(feat, anchor)
+            got.append(m.grads.clone())
+        assert torch.equal(got[0], got[1]) and torch.equal(got[0], got[2])
+        tok = got[0][off: off + shape[0] * shape[1]].view(shape)
+        sot, eot = m.cfg.vocab_size - 2, m.cfg.vocab_size - 1
+        assert tok[sot].abs().sum() > 0 and tok[eot].abs().sum() > 0
+
+
 def test_bench_two_ranks_on_rccl_when_the_box_has_two_gpus():
     """the first contact of the multi-rank step with RCCL.  ``bench.py --gpus 2 --backend nccl`` (its own launcher:
     torch.distributed.run, one rank per device, bucketed all-reduce behind the backward) on any box with >= 2 GPUs; the one-GPU test

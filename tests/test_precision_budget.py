@@ -14,7 +14,7 @@ by ``python tests/test_precision_budget.py``):
   block in fp32) leaves the worst row above 8.8e-4; getting the worst row under 7.5e-4 means block 0 entirely in higher precision
   (three MFMA passes per GEMM plus 32-bit q|k|v / hidden rows there: about +14 % of the search).
 
-The GPU's measured figure for the same kind of rows is in every bench line (``parity_rel_l2``)."""
+The GPU's measured figure for the same kind of rows is in every ``bench.py --full`` line (``parity_rel_l2``)."""
 import json
 import os
 import sys

@@ -21,7 +21,7 @@ for i in $(seq $R); do
   for ((a = 0; a < ${#args[@]}; a += 2)); do
     label=${args[a]}; envs=${args[a + 1]}
     # shellcheck disable=SC2086
-    env $envs timeout -k 10 300 python bench.py --steps $STEPS --warmup $WARM --no-cpu-baseline --no-dense-leg $EXTRA 2>/dev/null | tail -1 \
+    env $envs timeout -k 10 300 python bench.py --full --steps $STEPS --warmup $WARM --no-cpu-baseline --no-dense-leg $EXTRA 2>/dev/null | tail -1 \
       | python tools/bench_line.py "$label" $SMALL || exit 1
   done
 done

@@ -5,7 +5,7 @@
 set -e
 OUT=$1; shift
 export TMPDIR=/tmp
-BENCH="python3 $PWD/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-dense-leg $*"
+BENCH="python3 $PWD/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-dense-leg $*"
 run() { name=$1; shift; export LEAF_BENCH_JSON_OUT=$PWD/$OUT/$name.bench.json; rocprofv3 --pmc "$@" --kernel-trace --output-format csv -d $OUT/$name -o run -- $BENCH > $OUT/$name.log 2>&1; echo "pass $name done"; }
 mkdir -p $OUT
 if [ -z "$PMC_TRAFFIC_ONLY" ]; then
