@@ -114,6 +114,15 @@ int leaf_score_candidates(leaf_text_t h, const float* params, const void* w16_fw
                           int objective, int32_t* best_idx, float* best_feat, float* loss, void* ws, size_t ws_bytes,
                           leaf_stream_t s);
 
+/* Segmented top-n selection (leaf_amd/csrc/select.hip; Charmer's position pick and arg-max, leaf_amd/charmer.py): per row b of
+ * loss [B, ld] (fp32, device) the min(n, count[b]) largest of columns [0, count[b]) in descending order -- ties -> lower column
+ * first, NaN above every number (as torch.topk / torch.argmax) -- into idx / val [B, n]; unused slots: idx -1, val -inf.
+ * accumulate != 0 (n == 1 only): merge into the running (val[b], idx[b]) instead, replacing it only on a STRICTLY greater value
+ * (or when idx[b] < 0), column index reported as col_offset + j: a long row scored in column chunks keeps "first maximum wins".
+ * No arithmetic touches a value: the result equals a stable descending sort bit for bit. */
+int leaf_select_topk(const float* loss, int ld, const int32_t* count, int B, int n, int col_offset, int accumulate,
+                     int32_t* idx, float* val, leaf_stream_t s);
+
 /* Exact work skipping, part 2 ("prefix reuse"): a search candidate equals its clean caption at every
  * position before its first changed token, and under the causal mask those rows are identical at every layer.
  * leaf_text_forward_kv runs the clean captions once and keeps each layer's q|k|v rows in `kv` (leaf_text_kv_bytes);

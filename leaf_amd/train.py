@@ -29,6 +29,7 @@ import numpy as np
 import torch
 
 from .attacks import DEFAULT_V, attack_text
+from .charmer import attack_text_charmer
 from .step import allreduce_grads, get_reducer
 
 LATEST_CHECKPOINT_NAME = "epoch_latest.pt"
@@ -434,8 +435,7 @@ class MicroClip:
 # ----------------------------------------------------------------------------- the epoch loop
 def train_one_epoch_text_only(model, model_frozen, tokenizer, V, data, loss, epoch, optimizer, scaler, scheduler, args,
                               tb_writer=None):
-    if getattr(args, "use_charmer", False):
-        raise NotImplementedError("--use_charmer (per-sentence Charmer attack) is outside the accelerated path")
+    use_charmer = bool(getattr(args, "use_charmer", False))
     if getattr(args, "horovod", False):
         raise NotImplementedError("horovod is not supported; launch with torch.distributed.run (RCCL)")
     normalize_fare = bool(getattr(args, "normalize_fare", False))   # utils_AT.py:296,319
@@ -485,8 +485,16 @@ def train_one_epoch_text_only(model, model_frozen, tokenizer, V, data, loss, epo
             anchor_ready.record(side)
         anchor.record_stream(cur_stream)
         t0 = time.time()
-        _, adv_texts = attack_text(model, tokenizer, texts, anchor, device, objective='l2', n=args.rho, k=args.k_adv,
-                                   V=V, constrain=args.constrain, debug=False, anchor_ready=anchor_ready)
+        if use_charmer:
+            # --use_charmer (utils_AT.py:297-304): the Charmer attack against the frozen model's anchors -- normalised under
+            # --normalize_fare while the candidates' features are not (objective 'l2'), as the reference does -- for the whole batch
+            # in one batched call instead of one call per caption
+            cur_stream.wait_event(anchor_ready)
+            adv_texts, _ = attack_text_charmer(model, tokenizer, texts, anchor, objective='l2', n=args.rho, k=args.k_adv, V=V,
+                                               constrain=args.constrain)
+        else:
+            _, adv_texts = attack_text(model, tokenizer, texts, anchor, device, objective='l2', n=args.rho, k=args.k_adv,
+                                       V=V, constrain=args.constrain, debug=False, anchor_ready=anchor_ready)
         times.append(time.time() - t0)
         if i == 0 and os.environ.get("LEAF_DEBUG_DUMP_ADV"):   # test hook: this rank's first adversarial batch of the epoch
             with open(os.path.join(os.environ["LEAF_DEBUG_DUMP_ADV"], f"adv_epoch{epoch}_rank{getattr(args, 'rank', 0)}.txt"), "w") as f:
