@@ -1,4 +1,4 @@
-/* Diagnostic exports of the libraries under tools/diag/ (make -C leaf_amd/csrc variants | stamps | ...; -DLEAF_VARIANTS).
+/* Diagnostic exports of the libraries under tools/diag/ (make -C leaf_amd/csrc variants | stamps | qa_phases; -DLEAF_DIAG_EXPORTS).
  * NOT part of libleaf_hip.so and not part of the integration surface (include/leaf_hip.h): test hooks and tuning
  * knobs for tests/test_gpu_variants.py, the tile-plan test of tests/test_host_cpu.py and the measuring tools under tools/. */
 #ifndef LEAF_HIP_DIAG_H

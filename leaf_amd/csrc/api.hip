@@ -543,11 +543,7 @@ int forward_chunk(const leaf_text* h, const float* P, const uint16_t* W, const i
         if (qkv_gemm(l, rows, ln, b.a)) return 1;
         if (!fused_attn && kv.kv_self_rows) {
             kvl = b.qkv;
-#ifdef LEAF_COPY_MEMCPY   // A/B build: the runtime's copy (three dispatches per 15-MB copy)
-            LEAF_TRY(hipMemcpyAsync(kv.kv_copy + (size_t)l * kv.kv_stride, b.qkv, (size_t)kv.kv_self_rows * 3 * d * 2, hipMemcpyDeviceToDevice, s));
-#else
             LEAF_TRY(leaf_launch_copy_bytes(b.qkv, kv.kv_copy + (size_t)l * kv.kv_stride, (size_t)kv.kv_self_rows * 3 * d * 2, s));
-#endif
         }
         if (last && !out) break;          // K/V-only pass (clean captions for the cache): nothing consumes the rest
         if (last && h->last_trim && !kv.kv_write) {
@@ -945,7 +941,7 @@ extern "C" int leaf_op_qkv_attn(int dtype, const void* x16, const void* Wp, cons
     return leaf_check(leaf_launch_qkv_attn(qa, dtype, (hipStream_t)s), "qkv_attn");
 }
 // ---- diagnostic exports (include/leaf_hip_diag.h): only in the builds of `make variants` / `make stamps` ... under tools/diag/
-#ifdef LEAF_VARIANTS
+#ifdef LEAF_DIAG_EXPORTS
 extern "C" int leaf_debug_qkv_attn_plan(const int32_t* lens, int ctx, int s0, int n, int prefixed, int group, int group_off, int tile_rows,
                                         int ncap, int32_t* out) {
     return leaf_qkv_attn_plan(lens, ctx, s0, n, prefixed, group, group_off, tile_rows > 0 ? tile_rows : leaf_qkv_attn_tile_rows(),

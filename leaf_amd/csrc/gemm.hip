@@ -327,15 +327,6 @@ static bool use_gemm64(const GemmArgs& p) {
 int leaf_gemm_family(const GemmArgs& p, int epi) {
     static int use256h = -1;   // LEAF_GEMM256H=0: A/B and test switch (the two-stage kernel then takes the big launches)
     if (use256h < 0) { const char* e = getenv("LEAF_GEMM256H"); use256h = (e && e[0] == '0') ? 0 : 1; }
-#ifdef LEAF_VARIANTS         // diagnostic builds only (make variants): the round-3 two-workgroups-per-CU experiment, never in libleaf_hip.so
-    static int use_pp = -1;    // LEAF_GEMM_PP=1: the two-workgroups-per-CU 128 x 256 kernel (variants/gemm128pp.hip) takes the big launches
-    if (use_pp < 0) { const char* e = getenv("LEAF_GEMM_PP"); use_pp = (e && (e[0] == '1' || e[0] == '2')) ? 1 : 0; }
-    // LEAF_GEMM_PP=2: only the HBM-bound residual shape (out_proj: N = K = d), where the ping-pong kernel measured 5-9 % faster alone
-    static int pp_mode = -1;
-    if (pp_mode < 0) { const char* e = getenv("LEAF_GEMM_PP"); pp_mode = e ? atoi(e) : 0; }
-    const bool pp_shape = pp_mode != 2 || (p.N == p.K && (epi == EPI_RESID_LN || epi == EPI_RESID_F32));
-    if (use_pp && pp_shape && p.M > 0 && p.lda % 8 == 0 && p.ldb % 8 == 0 && leaf_gemm128pp_eligible(p, epi)) return 7;
-#endif
     if (use256h && p.M > 0 && p.lda % 8 == 0 && p.ldb % 8 == 0 && leaf_gemm256h_eligible(p, epi)) return 4;
     static int use256 = -1;
     if (use256 < 0) { const char* e = getenv("LEAF_GEMM256"); use256 = (e && e[0] == '0') ? 0 : 1; }
@@ -353,12 +344,6 @@ hipError_t leaf_launch_gemm(const GemmArgs& p_in, int dtype, int epi, hipStream_
     if (p.M <= 0 || p.N <= 0 || p.K <= 0 || p.N % BN || p.K % BK || p.lda % 8 || p.ldb % 8 || p.ldc % 4)
         return hipErrorInvalidValue;
     const int fam = leaf_gemm_family(p, epi);
-#ifdef LEAF_VARIANTS
-    if (fam == 7) return leaf_launch_gemm128pp(p, dtype, epi, s);
-    static int use_w4 = -1;    // LEAF_GEMM_W4=1: the four-wave 128 x 128-per-wave experiment (variants/gemm256w4.hip) where it is eligible
-    if (use_w4 < 0) { const char* e = getenv("LEAF_GEMM_W4"); use_w4 = (e && e[0] == '1') ? 1 : 0; }
-    if (use_w4 && fam == 4 && leaf_gemm256w4_eligible(p, epi)) return leaf_launch_gemm256w4(p, dtype, epi, s);
-#endif
     if (p.a_wrap && fam != 4) return hipErrorInvalidValue;      // only the half-stage ring kernel re-reads A (the caller duplicates it otherwise)
     if (fam == 4) return leaf_launch_gemm256h(p, dtype, epi, s);
     if (fam == 6) return leaf_launch_gemm64(p, dtype, epi, s);

@@ -97,11 +97,7 @@ __global__ __launch_bounds__(512, 2) void gemm_nt256_half_kernel(GemmArgs p) {
     set_sources(m0, n0, lane);
     const unsigned bstep = 16u * (unsigned)p.ldb;   // 8 rows, bytes
     const int piece = wid * 4096;
-#ifdef LEAF_DIAG_NODMA   // diagnostic only: no operand traffic at all (results are garbage) - isolates the MFMA + LDS-read loop
-#define DMA16(src, dst) asm volatile("" ::"v"(src), "v"(dst))
-#else
 #define DMA16(src, dst) __builtin_amdgcn_global_load_lds((glb_void_t*)(src), (lds_void_t*)(dst), 16, 0, 0)
-#endif
     // piece q (0..3) of half-stage u: u even = A panel of K tile u/2, u odd = B panel
     // (so = byte offset of the ring slot that half-stage lands in, kt = its K tile)
     // (A's k offset wraps after awrap K tiles -- GemmArgs::a_wrap, [A | A] operands; awrap >= nt otherwise: two scalar instructions per tile)
@@ -119,17 +115,9 @@ __global__ __launch_bounds__(512, 2) void gemm_nt256_half_kernel(GemmArgs p) {
     const int fo0 = lds_off_h(frow, fkc), fo1 = lds_off_h(frow, 4 + fkc);   // k-step 0 / 1 inside a 64-deep tile
     const int xbase = wm * 128 * 128, wbase = wn * 64 * 128;
     typedef typename TT::vec8 frag_t;
-#ifdef LEAF_DIAG_NOREAD
-    frag_t dummy_frag;
-    asm volatile("" : "=v"(dummy_frag));
-#endif
     frag_t Fx0, Fx1, Fx2, Fx3, Fx4, Fx5, Fx6, Fx7, Fw0, Fw1, Fw2, Fw3;
     frag_t Gx0, Gx1, Gx2, Gx3, Gx4, Gx5, Gx6, Gx7, Gw0, Gw1, Gw2, Gw3;
-#ifdef LEAF_DIAG_NOREAD   // diagnostic only: no fragment reads (stale registers feed the MFMAs)
-#define LD(ptr) (dummy_frag)
-#else
 #define LD(ptr) (*(const frag_t*)(ptr))
-#endif
     // fragments of one 32-deep k-step: A panel at ring offset sa, B panel at sb
 #define READ_FRAGS(P, sa, sb, fo)                                                                            \
     {                                                                                                        \
@@ -139,60 +127,24 @@ __global__ __launch_bounds__(512, 2) void gemm_nt256_half_kernel(GemmArgs p) {
         P##x0 = LD(sa_); P##x1 = LD(sa_ + 2048); P##x2 = LD(sa_ + 4096); P##x3 = LD(sa_ + 6144);             \
         P##x4 = LD(sa_ + 8192); P##x5 = LD(sa_ + 10240); P##x6 = LD(sa_ + 12288); P##x7 = LD(sa_ + 14336);   \
     }
-#define MROW(P, i, xi)                                                                                       \
-    acc[i][0] = TT::mfma(P##w0, xi, acc[i][0]); acc[i][1] = TT::mfma(P##w1, xi, acc[i][1]);                   \
-    acc[i][2] = TT::mfma(P##w2, xi, acc[i][2]); acc[i][3] = TT::mfma(P##w3, xi, acc[i][3]);
-#define MFMA_H1(P) MROW(P, 0, P##x0) MROW(P, 1, P##x1) MROW(P, 2, P##x2) MROW(P, 3, P##x3)
-#define MFMA_H2(P) MROW(P, 4, XSEL_4(P)) MROW(P, 5, XSEL_5(P)) MROW(P, 6, XSEL_6(P)) MROW(P, 7, XSEL_7(P))
+#define MROW(P, i)                                                                                           \
+    acc[i][0] = TT::mfma(P##w0, P##x##i, acc[i][0]); acc[i][1] = TT::mfma(P##w1, P##x##i, acc[i][1]);         \
+    acc[i][2] = TT::mfma(P##w2, P##x##i, acc[i][2]); acc[i][3] = TT::mfma(P##w3, P##x##i, acc[i][3]);
+#define MFMA_H2(P) MROW(P, 4) MROW(P, 5) MROW(P, 6) MROW(P, 7)
 #define SB __builtin_amdgcn_sched_barrier(0);
-#ifdef LEAF_DIAG_NOBAR    // diagnostic only: no per-tile workgroup barrier
-#define DIAG_BARRIER
-#else
-#define DIAG_BARRIER __builtin_amdgcn_s_barrier();
-#endif
 #define SYNC_TILE(cnt)                                                                                       \
     SB                                                                                                       \
     asm volatile("s_waitcnt vmcnt(" #cnt ") lgkmcnt(0)" ::: "memory");                                       \
-    DIAG_BARRIER                                                                                             \
+    __builtin_amdgcn_s_barrier();                                                                            \
     asm volatile("" ::: "memory");
     // one 32-deep k-step, software-pipelined at instruction granularity: the 12 fragment reads of this k-step (CUR) are
     // issued ONE AT A TIME in the shadow of individual MFMAs - first under the second half (rows 4-7) of the previous
     // k-step's MFMAs, the last four (rows 4-7 of CUR, not needed before the next k-step) under CUR's own first half -
-    // instead of twelve back-to-back ds_read_b128 that stall the wave's in-order MFMA issue (diagnostic builds: the
-    // bunched reads cost 10 % of a tile).  The four DMA pieces of a half-stage are spread in between (IS = issue macro).
-#ifdef LEAF_DIAG_READ23   // diagnostic only (wrong results): activation-fragment rows 4-7 reuse the registers of rows 0-3, i.e. 8 instead
-                          // of 12 ds_read_b128 per k-step = the LDS read bytes per MFMA of a 128 x 128 per-wave tile (256 B), on random data
-#define XSEL_0(P) P##x0
-#define XSEL_1(P) P##x1
-#define XSEL_2(P) P##x2
-#define XSEL_3(P) P##x3
-#define XSEL_4(P) P##x0
-#define XSEL_5(P) P##x1
-#define XSEL_6(P) P##x2
-#define XSEL_7(P) P##x3
-#define RDX(P, n) if ((n) < 4) { P##x##n = LD(sa_ + (n) * 2048); }
-#else
-#define XSEL_0(P) P##x0
-#define XSEL_1(P) P##x1
-#define XSEL_2(P) P##x2
-#define XSEL_3(P) P##x3
-#define XSEL_4(P) P##x4
-#define XSEL_5(P) P##x5
-#define XSEL_6(P) P##x6
-#define XSEL_7(P) P##x7
+    // instead of twelve back-to-back ds_read_b128 that stall the wave's in-order MFMA issue (bunched, the reads
+    // cost 10 % of a tile).  The four DMA pieces of a half-stage are spread in between (IS = issue macro).
 #define RDX(P, n) P##x##n = LD(sa_ + (n) * 2048);
-#endif
-#define MF(P, i, j) acc[i][j] = TT::mfma(P##w##j, XSEL_##i(P), acc[i][j]);
+#define MF(P, i, j) acc[i][j] = TT::mfma(P##w##j, P##x##i, acc[i][j]);
 #define RDW(P, n) P##w##n = LD(sb_ + (n) * 2048);
-#ifdef LEAF_GEMM_BUNCHED_READS   // the previous schedule, kept for A/B builds
-#define KSTEP(PREV, CUR, sa, sb, fo, IS0, IS1, IS2, IS3)                                                     \
-    READ_FRAGS(CUR, sa, sb, fo)                                                                              \
-    SB MROW(PREV, 4, PREV##x4) SB IS0                                                                        \
-    SB MROW(PREV, 5, PREV##x5) SB IS1                                                                        \
-    SB MROW(PREV, 6, PREV##x6) SB IS2                                                                        \
-    SB MROW(PREV, 7, PREV##x7) SB IS3                                                                        \
-    SB MFMA_H1(CUR)
-#else
 #define KSTEP(PREV, CUR, sa, sb, fo, IS0, IS1, IS2, IS3)                                                     \
     {                                                                                                        \
         const char* sa_ = smem + (sa) + xbase + (fo);                                                        \
@@ -203,12 +155,11 @@ __global__ __launch_bounds__(512, 2) void gemm_nt256_half_kernel(GemmArgs p) {
         SB IS1                                                                                               \
         SB MF(PREV, 6, 0) SB RDX(CUR, 2) SB MF(PREV, 6, 1) MF(PREV, 6, 2) SB RDX(CUR, 3) SB MF(PREV, 6, 3)    \
         SB IS2                                                                                               \
-        SB MROW(PREV, 7, XSEL_7(PREV)) SB IS3                                                              \
+        SB MROW(PREV, 7) SB IS3                                                                              \
         SB MF(CUR, 0, 0) SB RDX(CUR, 4) SB MF(CUR, 0, 1) MF(CUR, 0, 2) SB RDX(CUR, 5) SB MF(CUR, 0, 3)        \
         SB MF(CUR, 1, 0) SB RDX(CUR, 6) SB MF(CUR, 1, 1) MF(CUR, 1, 2) SB RDX(CUR, 7) SB MF(CUR, 1, 3)        \
-        SB MROW(CUR, 2, XSEL_2(CUR)) MROW(CUR, 3, XSEL_3(CUR)) SB                                                    \
+        SB MROW(CUR, 2) MROW(CUR, 3) SB                                                                      \
     }
-#endif
 #define NOP_
 
     const int nt = p.K / BK;   // K tiles, >= 4 (host-checked)
@@ -250,7 +201,7 @@ __global__ __launch_bounds__(512, 2) void gemm_nt256_half_kernel(GemmArgs p) {
     STAMP(1)
     READ_FRAGS(G, sa, sb, fo0)
     SB ISSUE_B(i0, 1, 0); ISSUE_B(i0, 1, 1); SB
-    MROW(G, 0, Gx0) MROW(G, 1, Gx1) SB ISSUE_B(i0, 1, 2); ISSUE_B(i0, 1, 3); SB MROW(G, 2, Gx2) MROW(G, 3, Gx3)
+    MROW(G, 0) MROW(G, 1) SB ISSUE_B(i0, 1, 2); ISSUE_B(i0, 1, 3); SB MROW(G, 2) MROW(G, 3)
     KSTEP(G, F, sa, sb, fo1, ISSUE_A(i1, 2, 0);, ISSUE_A(i1, 2, 1);, ISSUE_A(i1, 2, 2);, ISSUE_A(i1, 2, 3);)
     ADV(sa) ADV(sb) ADV(i0) ADV(i1)
     // ---- tiles 1 .. nt-3: request B of tile T+1 and A of tile T+2
@@ -435,10 +386,6 @@ __global__ __launch_bounds__(512, 2) void gemm_nt256_half_kernel(GemmArgs p) {
                     fv[it] = *(const u32x4_t*)(sl + row * 128 + (pc << 4));
                 }
                 const int m = mb + 64 * pass + row;
-#ifdef LEAF_DIAG_NOQKVSTORE   // diagnostic only (garbage results): the QKV GEMM computes and stages its tile but never stores it -- with
-                              // LEAF_DIAG_ATTN_L2 an upper bound on what fusing QKV GEMM -> attention could save
-                if constexpr (EPI == EPI_LNFOLD_T) { asm volatile("" ::"v"(fv[it]), "v"(m)); } else
-#endif
                 if (m < p.M)
                     __builtin_nontemporal_store(fv[it], (u32x4_t*)(dst + (size_t)m * p.ldc + nb + ((pc ^ (row & 7)) << 3)));
             }
@@ -553,12 +500,7 @@ __global__ __launch_bounds__(512, 2) void gemm_nt256_half_kernel(GemmArgs p) {
                     v.x = __builtin_fmaf(res[it].x, beta, v.x); v.y = __builtin_fmaf(res[it].y, beta, v.y);
                     v.z = __builtin_fmaf(res[it].z, beta, v.z); v.w = __builtin_fmaf(res[it].w, beta, v.w);
                 }
-#ifdef LEAF_DIAG_NOF32STORE   // diagnostic only (garbage results): the residual GEMM with statistics never stores its fp32 rows -- the byte
-                              // volume of a residual stream kept as the 16-bit copy + an 8-bit extension (8 d instead of 12 d per row)
-                if (m < p.M && EPI != EPI_RESID_LN) {
-#else
                 if (m < p.M) {
-#endif
                     typedef float f32x4_t __attribute__((ext_vector_type(4)));
                     __builtin_nontemporal_store(f32x4_t{v.x, v.y, v.z, v.w}, (f32x4_t*)((float*)p.C + (size_t)m * p.ldc + nb + ((pc ^ (row & 15)) << 2)));
                 }
@@ -568,13 +510,8 @@ __global__ __launch_bounds__(512, 2) void gemm_nt256_half_kernel(GemmArgs p) {
                     const float gq = row16_sum(lnfold_dev4(v.x, v.y, v.z, v.w, gs * (1.0f / 64.0f)));
                     if (m < p.M) {
                         typedef unsigned u32x2_t __attribute__((ext_vector_type(2)));
-#ifdef LEAF_X16_REGULAR   // A/B build: the 16-bit copy (re-read by the next GEMM) through the cache hierarchy instead of around it
-                        *(u32x2_t*)((u16*)p.x16 + (size_t)m * p.ldx16 + nb + ((pc ^ (row & 15)) << 2)) =
-                            __builtin_bit_cast(u32x2_t, pack4<TT>(v.x, v.y, v.z, v.w));
-#else
                         __builtin_nontemporal_store(__builtin_bit_cast(u32x2_t, pack4<TT>(v.x, v.y, v.z, v.w)),
                                                     (u32x2_t*)((u16*)p.x16 + (size_t)m * p.ldx16 + nb + ((pc ^ (row & 15)) << 2)));
-#endif
                         if (pc == 0) p.stat_out[(size_t)(nb >> 6) * p.stat_ld + m] = float2{gs, gq};
                     }
                 }
@@ -586,9 +523,6 @@ __global__ __launch_bounds__(512, 2) void gemm_nt256_half_kernel(GemmArgs p) {
     if (!has_next) break;
     // exactly NSTORE stores behind the prefetch: a full tile without the optional pre-activation stash
     counted = (m0 + BM <= p.M) && !(EPI == EPI_ACT_T && p.aux);
-#ifdef LEAF_DIAG_NOQKVSTORE
-    if constexpr (EPI == EPI_LNFOLD_T) counted = false;
-#endif
     first = false;
     v = v_next; m0 = m0_next; n0 = n0_next;
   }
@@ -601,21 +535,12 @@ __global__ __launch_bounds__(512, 2) void gemm_nt256_half_kernel(GemmArgs p) {
 #undef ISSUE_HALF_B
 #undef READ_FRAGS
 #undef MROW
-#undef MFMA_H1
 #undef MFMA_H2
 #undef SYNC_TILE
 #undef KSTEP
 #undef MF
 #undef RDW
 #undef RDX
-#undef XSEL_0
-#undef XSEL_1
-#undef XSEL_2
-#undef XSEL_3
-#undef XSEL_4
-#undef XSEL_5
-#undef XSEL_6
-#undef XSEL_7
 #undef NOP_
 #undef SB
 #undef LD

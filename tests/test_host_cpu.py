@@ -63,8 +63,8 @@ def test_c_abi_exports_every_declared_symbol():
         assert hasattr(l, name), f"{name} declared in include/leaf_hip.h but not exported"
     assert declared == set(_lib.EXPORTS), declared ^ set(_lib.EXPORTS)
     assert l.leaf_version() >= 1
-    # the product library carries no experiment and no diagnostic export: those live in the builds under
-    # tools/diag/ (include/leaf_hip_diag.h, leaf_amd/csrc/variants/)
+    # the product library carries no experiment and no diagnostic export: the exports live in the builds under
+    # tools/diag/ (include/leaf_hip_diag.h)
     import subprocess
     syms = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], capture_output=True, text=True, check=True).stdout
     exported = set(re.findall(r" T (leaf_[A-Za-z0-9_]+)", syms))
@@ -119,7 +119,7 @@ def test_handle_layout_and_errors_without_gpu():
 def test_every_kernel_sets_the_fp16_saturation_mode_first():
     """ADVICE r5: F16::pack2 (common.h) leaves the +-65504 saturation to the hardware -- MODE.FP16_OVFL, which a wave only has after
     ``leaf_fp16_sat_mode()``.  A kernel that forgets the call would turn an overflow into inf / NaN activations silently, so the
-    convention is linted: the first statement of EVERY ``__global__`` body under leaf_amd/csrc (product and variants) is that call."""
+    convention is linted: the first statement of EVERY ``__global__`` body under leaf_amd/csrc is that call."""
     import glob
 
     def close(s, i):               # index of the parenthesis that closes the one at s[i]
@@ -144,6 +144,25 @@ def test_every_kernel_sets_the_fp16_saturation_mode_first():
                 bad.append((os.path.relpath(f, ROOT), s[:m.start()].count("\n") + 1))
     assert n >= 50, f"only {n} kernels found: the lint's pattern no longer matches the sources"
     assert not bad, f"kernels that do not start with leaf_fp16_sat_mode(): {bad}"
+
+
+def test_sources_compile_only_the_product_and_the_stamp_builds():
+    """The kernels hold only what runs: no compile switch that builds a garbage-result diagnostic or an A/B experiment (retired after
+    28efbe6, profiles/HISTORY.md).  The conditionals left are the include guards and the three correct-result diagnostic builds."""
+    import glob
+    allowed = {"__cplusplus", "LEAF_GEMM_STAMPS", "LEAF_QA_PHASES", "LEAF_DIAG_EXPORTS"}
+    files = glob.glob(os.path.join(ROOT, "leaf_amd", "csrc", "**", "*.hip"), recursive=True)
+    files += glob.glob(os.path.join(ROOT, "leaf_amd", "csrc", "**", "*.h"), recursive=True)
+    files += glob.glob(os.path.join(ROOT, "include", "*.h"))
+    bad = set()
+    for f in files:
+        for cond in re.findall(r"^\s*#\s*(?:if|ifdef|ifndef|elif)\b([^\n]*)", open(f).read(), re.M):
+            for name in set(re.findall(r"[A-Za-z_]\w*", cond.split("//")[0])) - {"defined"}:
+                if name not in allowed and not re.fullmatch(r"LEAF_\w+_H", name):
+                    bad.add((os.path.relpath(f, ROOT), name))
+    assert len(files) >= 20
+    assert not bad, sorted(bad)
+    assert not os.path.exists(os.path.join(ROOT, "leaf_amd", "csrc", "variants"))
 
 
 def test_product_has_no_oracle_or_cpu_fallback():

@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """In-loop rate and per-tile overhead of a 256 x 256 GEMM kernel from the SLOPE of time over K (round 5): the same M x N at K, 2K, 4K --
-t(K) = overhead + K / rate.  Runs this repo's kernel (the bias + 16-bit store epilogue; LEAF_GEMM_W4=1 with the diagnostic build selects
-the four-wave experiment) and the vendor library (torch.matmul -> hipBLASLt) on the same operands.
-    [LEAF_HIP_LIB=tools/diag/libleaf_hip_variants.so LEAF_GEMM_W4=1] python tools/kloop_rate.py"""
+t(K) = overhead + K / rate.  Runs this repo's kernel (the bias + 16-bit store epilogue) and the vendor library (torch.matmul ->
+hipBLASLt) on the same operands.
+    python tools/kloop_rate.py"""
 import ctypes as C
 import os
 import sys
@@ -30,7 +30,7 @@ def main():
     dev = torch.device("cuda:0")
     st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
     M = int(os.environ.get("ROWS", "107520"))
-    print("LEAF_GEMM_W4 =", os.environ.get("LEAF_GEMM_W4", "0"), "| LEAF_GEMM_PERSIST =", os.environ.get("LEAF_GEMM_PERSIST", "1"), "| rows", M)
+    print("LEAF_GEMM_PERSIST =", os.environ.get("LEAF_GEMM_PERSIST", "1"), "| rows", M)
     for N in (768, 3072):
         Ks = [768, 1536, 3072, 6144]
         rows = {"ours": [], "vendor": []}
