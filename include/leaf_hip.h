@@ -48,7 +48,7 @@ int leaf_text_set_chunk(leaf_text_t h, int seqs_per_chunk); /* sequences process
 /* options: "chunk" (as above), "last_layer_trim" (0/1, default 1: the last block's attention output, out-projection and
  * MLP are computed for the pooled EOT row only -- exact, every op after attention is row-wise), "compact_resid" (0/1, default 1:
  * the residual stream of the LN-folded forward-only passes as the 16-bit copy + a remainder byte per element instead of an fp32
- * row beside that copy -- see leaf_op_gemm_resid_ln8 below; 0, or LEAF_COMPACT_RESID=0, keeps fp32 rows), and the A/B switches "streams", "ln_fold", "fuse_attn", "normalize_fare" */
+ * row beside that copy -- see leaf_op_gemm_resid_ln8 below; 0, or LEAF_COMPACT_RESID=0, keeps fp32 rows), "single_edit" (0/1, default 0: see "single-edit passes" below), and the A/B switches "streams", "ln_fold", "fuse_attn", "normalize_fare" */
 int leaf_text_set_option(leaf_text_t h, const char* name, int value);
 /* current value of an option of leaf_text_set_option (+ "split_blocks"); -1 = unknown name */
 int leaf_text_get_option(leaf_text_t h, const char* name);
@@ -151,6 +151,21 @@ int leaf_score_candidates_prefix_fused(leaf_text_t h, const float* params, const
                                        const int32_t* seq_lens, const int32_t* cu_rows, const int32_t* prefix, int max_len,
                                        const float* anchor, int B, int rho, int objective, int32_t* best_idx, float* best_feat,
                                        float* loss, void* kv, size_t kv_bytes, void* ws, size_t ws_bytes, leaf_stream_t s);
+
+/* Exact work skipping, part 3 ("single-edit passes"; option "single_edit" of leaf_text_set_option, 0/1, default 0, set by the caller
+ * for the passes it holds for).  Block 0's q|k|v row is LN1(E[token] + P[position]) W_qkv + b: it depends on the pair (token,
+ * position) and on nothing else.  With the option set the caller PROMISES, for every candidate i of a leaf_score_candidates_prefix /
+ * _prefix_fused pass, that it is its caption with ONE token replaced at position prefix[i]: equal lengths, and every token BEHIND
+ * prefix[i] equal to the caption's at the same position (in front of it: the promise prefix reuse makes already).  Of the rows a
+ * candidate computes only row prefix[i] then has a pair its caption does not have; block 0 projects that one row per candidate (one
+ * small GEMM) and its attention reads every other q|k|v row -- Q included -- from layer 0 of the captions' cache.  Every later
+ * block is unchanged and the results are bit-identical.  The cache must hold the captions' Q rows of layer 0: leaf_text_forward_kv
+ * writes them; leaf_score_candidates_prefix_fused writes them only when it runs with the option set itself (without it the captions' Q rows never
+ * leave the chip), so a cache from a fused pass WITHOUT the option must not be handed to a pass WITH it (leaf_amd/model.py keeps
+ * that flag beside the cache and refuses).  The engine cannot check the promise (the tokens are on the device); a broken one gives
+ * wrong scores.  Passes the mode does not take (ln_fold = 0, dense rows, no prefix map, a one-block tower) run as without the
+ * option.  For token-level substitutions (leaf_amd/step.py, the benchmark's synthetic search); NOT for the character-level string
+ * search (leaf_amd/attacks.py, charmer.py): a character edit re-tokenises the rest of the caption. */
 
 /* training forward (utils_AT.py:317-319) keeping activations in `stash` for the backward pass */
 int leaf_text_forward_train(leaf_text_t h, const float* params, const void* w16_fwd, const int32_t* tokens,

@@ -119,6 +119,7 @@ extern "C" int leaf_text_set_option(leaf_text_t h, const char* name, int value) 
     }
     if (!strcmp(name, "fuse_attn")) { h->fuse_attn = value ? 1 : 0; return 0; }
     if (!strcmp(name, "compact_resid")) { h->compact_resid = value ? 1 : 0; return 0; }
+    if (!strcmp(name, "single_edit")) { h->single_edit = value ? 1 : 0; return 0; }
     leaf_set_error("unknown option '%s'", name);
     return 1;
 }
@@ -132,6 +133,7 @@ extern "C" int leaf_text_get_option(leaf_text_t h, const char* name) {
     if (!strcmp(name, "ln_fold")) return h->ln_fold;
     if (!strcmp(name, "fuse_attn")) return h->fuse_attn;
     if (!strcmp(name, "compact_resid")) return h->compact_resid;
+    if (!strcmp(name, "single_edit")) return h->single_edit;
     if (!strcmp(name, "split_blocks")) return h->split_blocks;
     return -1;
 }
@@ -493,10 +495,36 @@ int forward_chunk(const leaf_text* h, const float* P, const uint16_t* W, const i
         if (epi == EPI_RESID_F32 || (l8 && !g)) return 0;
         return leaf_check(leaf_launch_ln_finalize(gl->stat_out, gl->stat_ld, m, d / 64, gl->eps, const_cast<float2*>(gl->rowstat), s), "ln_finalize");
     };
+    // Single-edit pass (engine.h single_edit): block 0 projects ONE row per sequence -- (token, position) at its prefix length, the only
+    // pair the caption does not have -- into a [cs, 3d] table and its attention looks every other row up in layer 0 of the captions'
+    // cache.  Taken for packed prefix passes of the LN-folded forward that have a cache to read; every other pass runs as before.
+    const bool edit = h->single_edit && fold && map.cu && map.prefix && map.base_cu && c.layers > 1 && !kv.kv_write &&
+                      (kv.kv_read || (kv.kv_copy && kv.kv_self_rows));
+    uint16_t* fresh = b.hh;          // the table: the hidden buffer is dead until block 0's c_fc
+    if (edit) {
+        // the chunk's own buffers serve as scratch (the full-row embedding pass below overwrites them): a derived row map with one row
+        // per sequence, starting at its prefix (cu = 0, 1, 2, .. in the pooled-position buffer, unused before the last block), gives
+        // the fresh rows with their 16-bit copy, statistics and -- for a split block 0 -- the [hi | lo | hi] copy (q|k|v scratch)
+        LEAF_TRY(leaf_launch_iota(b.eot, cs, s));
+        const RowMap one{b.eot, 0, 0, map.ctx, map.prefix + map.s0, nullptr, 1, 0};
+        LEAF_TRY(leaf_launch_embed_fold(tokens + (size_t)map.s0 * map.ctx, P + h->tok_emb, P + h->pos_emb, b.x, b.x16, b.stat, cs, cs, cs,
+                                        one, d, c.vocab_size, dt, s, nullptr, lo8, sq(0) ? b.qkv : nullptr));
+        LEAF_TRY(leaf_launch_ln_finalize(b.stat, cs, cs, d / 64, c.ln_eps, b.rowstat, s));
+        GemmLn q = ln; q.ln_s = sq(0) ? h->split_s_qkv(0) : h->fold_s_qkv(W, 0);
+        const int qK = sq(0) ? 3 * d : d;
+        if (leaf_gemm(dt, EPI_LNFOLD_T, sq(0) ? (const void*)b.qkv : (const void*)b.x16, qK, sq(0) ? h->split_qkv3(0) : W + h->w16_fold_qkv(0), qK,
+                      fresh, 3 * d, h->fold_c_qkv(W, 0), nullptr, cs, 3 * d, qK, 0, s, 0.f, 0, nullptr, &q)) return 1;
+    }
     if (fold) {
+        // (single-edit pass: nothing multiplies the [hi | lo | hi] copy of ALL rows any more -- 6 d bytes per row written and read once)
         LEAF_TRY(leaf_launch_embed_fold(tokens, P + h->tok_emb, P + h->pos_emb, b.x, b.x16, b.stat, rows, rows, cs, map, d,
-                                        c.vocab_size, dt, s, nullptr, lo8, sq(0) ? b.hh : nullptr));
+                                        c.vocab_size, dt, s, nullptr, lo8, sq(0) && !edit ? b.hh : nullptr));
         LEAF_TRY(leaf_launch_ln_finalize(b.stat, rows, rows, d / 64, c.ln_eps, b.rowstat, s));
+        // ... except the captions' rows of a fused first stage (the first rows of the chunk), whose q|k|v GEMM into the cache wants it:
+        // the same kernel over those rows alone (identical values for what it writes twice)
+        if (edit && sq(0) && kv.kv_self_rows)
+            LEAF_TRY(leaf_launch_embed_fold(tokens, P + h->tok_emb, P + h->pos_emb, b.x, b.x16, b.stat, rows, (int)kv.kv_self_rows, map.group_off,
+                                            map, d, c.vocab_size, dt, s, nullptr, lo8, b.qkv));
     }
     else
         LEAF_TRY(leaf_launch_embed_ln(tokens, P + h->tok_emb, P + h->pos_emb, P + o0.ln1_w, P + o0.ln1_b, c.ln_eps, b.x,
@@ -519,6 +547,17 @@ int forward_chunk(const leaf_text* h, const float* P, const uint16_t* W, const i
         const uint16_t* qB = q3 ? h->split_qkv3(l) : W + h->w16_fold_qkv(l);
         const float* qS = q3 ? h->split_s_qkv(l) : h->fold_s_qkv(W, l);
         const int qK = q3 ? 3 * d : d;
+        if (edit && l == 0) {
+            if (kv.kv_self_rows) {
+                // fused first stage: the captions' WHOLE q|k|v rows go to the cache (their own attention reads its Q from there too)
+                uint16_t* dst = kv.kv_copy;
+                GemmLn q = ln; q.ln_s = qS;
+                if (leaf_gemm(dt, EPI_LNFOLD_T, q3 ? (const void*)b.qkv : ln.x16, qK, qB, qK, dst, 3 * d, h->fold_c_qkv(W, l), nullptr,
+                              (int)kv.kv_self_rows, 3 * d, qK, 0, s, 0.f, 0, nullptr, &q)) return 1;
+                kvl = dst;
+            }
+            LEAF_TRY(leaf_launch_attention_fwd(fresh, kvl, b.a, cs, map, c.heads, d, dt, s, nullptr, max_len, 1));
+        } else
         if (fused_attn) {
             if (kv.kv_self_rows) {
                 // only the K and V thirds: nothing ever reads a caption's q rows from the cache (its own attention runs inside the
@@ -541,7 +580,8 @@ int forward_chunk(const leaf_text* h, const float* P, const uint16_t* W, const i
             if (leaf_qkv_attn(qa, dt, s)) return 1;
         } else
         if (qkv_gemm(l, rows, ln, b.a)) return 1;
-        if (!fused_attn && kv.kv_self_rows) {
+        const bool attn_done = fused_attn || (edit && l == 0);
+        if (!attn_done && kv.kv_self_rows) {
             kvl = b.qkv;
             LEAF_TRY(leaf_launch_copy_bytes(b.qkv, kv.kv_copy + (size_t)l * kv.kv_stride, (size_t)kv.kv_self_rows * 3 * d * 2, s));
         }
@@ -595,7 +635,7 @@ int forward_chunk(const leaf_text* h, const float* P, const uint16_t* W, const i
                                               nullptr, cs, map, d, c.embed_dim, normalize, s, /*rows_are_pooled=*/1));
             return 0;
         }
-        if (!fused_attn) LEAF_TRY(leaf_launch_attention_fwd(b.qkv, kvl, b.a, cs, map, c.heads, d, dt, s, nullptr, max_len));
+        if (!attn_done) LEAF_TRY(leaf_launch_attention_fwd(b.qkv, kvl, b.a, cs, map, c.heads, d, dt, s, nullptr, max_len));
         if (out_gemm(l, b.a, b.x, rows, &ln)) return 1;
         if (!fold) LEAF_TRY(leaf_launch_layernorm(b.x, P + o.ln2_w, P + o.ln2_b, c.ln_eps, b.a, rows, d, dt, s));
         if (fc_gemm(l, rows, ln, b.a, b.hh)) return 1;

@@ -60,11 +60,14 @@ __device__ __forceinline__ s16x4 load_vt_frag(const char* vlds, int key0, int di
     }
 }
 
-template <class TT, bool USE_TR, int MAXT>
-__global__ __launch_bounds__(256) void attn_fwd_kernel(const u16* __restrict__ qkv, const u16* __restrict__ kv_base,
-                                                       u16* __restrict__ out, int n_items, RowMap map, int heads, int d,
-                                                       const int32_t* __restrict__ eot_pos, int vrows) {
-    leaf_fp16_sat_mode();
+// EDIT (single-edit scoring passes, block 0; api.hip): a sequence's q|k|v rows are not computed but looked up.  qkv is then a
+// [sequences of the launch, 3d] table with ONE row per sequence -- the row of its edited position (= its prefix length) -- and
+// every other position, before AND behind the edit, reads the clean caption's row from kv_base (all three thirds, Q included).
+// Sequences in front of map.group_off are the captions themselves: cache rows only.  Same body, same bits.
+template <class TT, bool USE_TR, int MAXT, bool EDIT>
+__device__ __forceinline__ void attn_fwd_body(const u16* __restrict__ qkv, const u16* __restrict__ kv_base,
+                                              u16* __restrict__ out, int n_items, RowMap map, int heads, int d,
+                                              const int32_t* __restrict__ eot_pos, int vrows) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
     const int item = blockIdx.x * 4 + wid;
@@ -77,9 +80,14 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const u16* __restrict__ q
     const int pfx = seq_prefix(map, sg);            // positions < pfx: K/V from the clean caption's cache
     int ctx = pfx + seq_len(map, sg);               // total length of this sequence
     ctx = ctx < vrows ? ctx : vrows;                // never past the LDS image (the host sizes vrows from the true maximum)
-    const u16* own = qkv + (size_t)row_s * ld + h * HD;
-    const u16* cached = pfx ? kv_base + (size_t)map.base_cu[(sg - map.group_off) / map.group] * ld + h * HD : own;
-    auto rowptr = [&](int pos) { return pos < pfx ? cached + (size_t)pos * ld : own + (size_t)(pos - pfx) * ld; };
+    const u16* own = qkv + (size_t)(EDIT ? n : row_s) * ld + h * HD;
+    const bool caption = EDIT && sg < map.group_off;
+    const int edit_pos = caption ? -1 : pfx;        // EDIT: the one position read from the sequence's own (fresh) row
+    const u16* cached = (EDIT || pfx) ? kv_base + (size_t)map.base_cu[caption ? sg : (sg - map.group_off) / map.group] * ld + h * HD : own;
+    auto rowptr = [&](int pos) -> const u16* {
+        if constexpr (EDIT) return pos == edit_pos ? own : cached + (size_t)pos * ld;
+        else return pos < pfx ? cached + (size_t)pos * ld : own + (size_t)(pos - pfx) * ld;
+    };
     const int r16 = lane & 15, g = lane >> 4;
     const int nt = (ctx + 15) >> 4;
     // query tiles below the prefix are not needed; with eot_pos (last layer: only the pooled row is consumed downstream)
@@ -186,11 +194,27 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const u16* __restrict__ q
     }
 }
 
+template <class TT, bool USE_TR, int MAXT>
+__global__ __launch_bounds__(256) void attn_fwd_kernel(const u16* __restrict__ qkv, const u16* __restrict__ kv_base,
+                                                       u16* __restrict__ out, int n_items, RowMap map, int heads, int d,
+                                                       const int32_t* __restrict__ eot_pos, int vrows) {
+    leaf_fp16_sat_mode();
+    attn_fwd_body<TT, USE_TR, MAXT, false>(qkv, kv_base, out, n_items, map, heads, d, eot_pos, vrows);
+}
+template <class TT, bool USE_TR, int MAXT>
+__global__ __launch_bounds__(256) void attn_edit_kernel(const u16* __restrict__ fresh, const u16* __restrict__ kv_base,
+                                                        u16* __restrict__ out, int n_items, RowMap map, int heads, int d,
+                                                        const int32_t* __restrict__ eot_pos, int vrows) {
+    leaf_fp16_sat_mode();
+    attn_fwd_body<TT, USE_TR, MAXT, true>(fresh, kv_base, out, n_items, map, heads, d, eot_pos, vrows);
+}
+
 }  // namespace
 
 hipError_t leaf_launch_attention_fwd(const void* qkv, const void* kv_base, void* out, int n_seq, RowMap map, int heads,
-                                     int d, int dtype, hipStream_t s, const int32_t* eot_pos, int max_len) {
+                                     int d, int dtype, hipStream_t s, const int32_t* eot_pos, int max_len, int single_edit) {
     if (d != heads * HD || map.ctx > 16 * MAXT_ALL || map.ctx < 1) return hipErrorInvalidValue;
+    if (single_edit && (!kv_base || !map.prefix || !map.base_cu || map.group < 1)) return hipErrorInvalidValue;
     if (max_len <= 0 || max_len > map.ctx) max_len = map.ctx;
     const int vrows = (max_len + 15) / 16 * 16;
     static int use_tr = -1;
@@ -202,16 +226,21 @@ hipError_t leaf_launch_attention_fwd(const void* qkv, const void* kv_base, void*
     const dim3 grid((items + 3) / 4), blk(256);
     const size_t lds = 4 * (size_t)wave_lds_bytes(vrows);
     const size_t lds_max = 4 * (size_t)wave_lds_bytes(96);
-#define LEAF_ATTN(TT, TR, MT)                                                                               \
+#define LEAF_ATTN_K(KERNEL, TT, TR, MT)                                                                     \
     do {                                                                                                    \
         static bool attr = false;                                                                           \
         if (!attr) {                                                                                        \
-            (void)hipFuncSetAttribute((const void*)attn_fwd_kernel<TT, TR, MT>,                             \
+            (void)hipFuncSetAttribute((const void*)KERNEL<TT, TR, MT>,                                      \
                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max);            \
             attr = true;                                                                                    \
         }                                                                                                   \
-        hipLaunchKernelGGL((attn_fwd_kernel<TT, TR, MT>), grid, blk, lds, s, (const u16*)qkv, (const u16*)kv_base,  \
+        hipLaunchKernelGGL((KERNEL<TT, TR, MT>), grid, blk, lds, s, (const u16*)qkv, (const u16*)kv_base,   \
                            (u16*)out, items, map, heads, d, eot_pos, vrows);                                \
+    } while (0)
+#define LEAF_ATTN(TT, TR, MT)                                                                               \
+    do {                                                                                                    \
+        if (single_edit) LEAF_ATTN_K(attn_edit_kernel, TT, TR, MT);                                         \
+        else LEAF_ATTN_K(attn_fwd_kernel, TT, TR, MT);                                                      \
     } while (0)
 #define LEAF_ATTN_T(TT, TR)                                                                                 \
     switch (vrows / 16) {                                                                                   \
@@ -225,5 +254,6 @@ hipError_t leaf_launch_attention_fwd(const void* qkv, const void* kv_base, void*
     else                   { if (use_tr) { LEAF_ATTN_T(BF16, true); } else { LEAF_ATTN_T(BF16, false); } }
 #undef LEAF_ATTN_T
 #undef LEAF_ATTN
+#undef LEAF_ATTN_K
     return hipGetLastError();
 }

@@ -624,6 +624,20 @@ hipError_t leaf_launch_copy_bytes(const void* src, void* dst, size_t bytes, hipS
     return hipGetLastError();
 }
 
+// out[i] = i: the row offsets of a RowMap with one row per sequence (api.hip, the fresh rows of a single-edit pass)
+namespace {
+__global__ __launch_bounds__(256) void iota_kernel(int32_t* __restrict__ out, int n) {
+    leaf_fp16_sat_mode();
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < n) out[i] = i;
+}
+}  // namespace
+hipError_t leaf_launch_iota(int32_t* out, int n, hipStream_t s) {
+    if (n < 1) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(iota_kernel, dim3((n + 255) / 256), dim3(256), 0, s, out, n);
+    return hipGetLastError();
+}
+
 // ---- operand splits of the optional higher-precision blocks (leaf_text_split_pack / option "split blocks"):
 // a fp32 value v as hi = 16-bit(v), lo = 16-bit(v - hi); hi + lo carries ~22 significand bits.  The GEMM then multiplies
 // [x_hi | x_lo | x_hi] by [W_hi | W_hi | W_lo] over a three times longer K: the fp32 accumulator receives x_hi W_hi + x_lo W_hi +

@@ -34,6 +34,10 @@ struct leaf_text {
     // restores the two kernels around the [rows, 3d] buffer.  The M-tile plan of a pass (first sequence of every tile) is cut on
     // the host and travels through a small ring of pinned buffers (an event per slot guards its re-use).
     int fuse_attn = 1;
+    // Single-edit scoring passes (option 'single_edit', include/leaf_hip.h): the caller promises that every candidate of the pass is
+    // its caption with ONE token replaced at position prefix[i].  Block 0's q|k|v row depends on (token, position) alone, so only
+    // that one row per candidate is projected; every other row is read from layer 0 of the captions' cache (api.hip forward_chunk).
+    int single_edit = 0;
     static constexpr int PLAN_RING = 8;
     int32_t* plan_host[PLAN_RING] = {};
     hipEvent_t plan_ev[PLAN_RING] = {};

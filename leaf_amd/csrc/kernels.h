@@ -131,6 +131,7 @@ hipError_t leaf_launch_score(const float* feat, const float* anchor, int B, int 
                              int32_t* best_idx, float* best_feat, float* loss, hipStream_t s);
 // device-to-device byte copy in one launch
 hipError_t leaf_launch_copy_bytes(const void* src, void* dst, size_t bytes, hipStream_t s);
+hipError_t leaf_launch_iota(int32_t* out, int n, hipStream_t s);      // out[i] = i
 // optional higher-precision blocks (hi + lo operand splits over a 3x longer K): out[rows, 3 d] = [hi | lo | hi] of x[rows, d];
 // weight rows W'[n,:] = (g .* W)[n,:] as [hi | hi | lo] + s[n] = sum (hi + lo) (triple), or the lo halves alone
 hipError_t leaf_launch_split16_rows(const float* x, void* out, int rows, int d, int dtype, hipStream_t s);
@@ -144,8 +145,11 @@ hipError_t leaf_launch_cast(const float* src, void* dst, size_t n, int dtype, hi
 // kv_base: this layer's qkv rows of the clean captions (prefix mode, map.prefix != null) or null
 // eot_pos (device, per sequence of the launch, absolute position) != null: compute only that query row of each sequence
 // and write it to out[sequence] (last-layer trimming)
+// single_edit: qkv is a [n_seq, 3d] table, ONE row per sequence (its position map.prefix[s]); every other position of a sequence,
+// its Q included, is read from the caption's rows in kv_base; sequences in front of map.group_off read kv_base only
 hipError_t leaf_launch_attention_fwd(const void* qkv, const void* kv_base, void* out, int n_seq, RowMap map, int heads,
-                                     int d, int dtype, hipStream_t s, const int32_t* eot_pos = nullptr, int max_len = 0);
+                                     int d, int dtype, hipStream_t s, const int32_t* eot_pos = nullptr, int max_len = 0,
+                                     int single_edit = 0);
 // eot_pos[n] = first index of the maximum token id among the kept positions (torch argmax pooling)
 hipError_t leaf_launch_eot_positions(const int32_t* tokens, int32_t* eot_pos, int n_seq, RowMap map, hipStream_t s);
 // out[n,:] = x[row of position eot_pos[n] of sequence n,:]   (fp32)

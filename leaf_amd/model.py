@@ -76,6 +76,35 @@ def _ptr(t: Optional[torch.Tensor]):
     return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
 
 
+def verify_single_edit(cand_tokens, cand_lens, prefix, base_tokens, base_lens, rho: int) -> None:
+    """The promise of a ``single_edit`` scoring pass, checked on the tokens (``LEAF_VERIFY_SINGLE_EDIT=1``; tests and debugging: the
+    comparison needs the tokens on the host): candidate ``i`` belongs to caption ``i // rho``, has the caption's length, and differs
+    from it at position ``prefix[i]`` at most -- every kept position in front of it AND behind it carries the caption's token.
+    Raises ``ValueError`` naming the first offender.  Arrays or tensors; works without a GPU."""
+    def host(x):
+        return np.asarray(x.cpu() if isinstance(x, torch.Tensor) else x)
+    cand, base = host(cand_tokens), host(base_tokens)
+    cand = cand.reshape(-1, cand.shape[-1])
+    base = base.reshape(-1, base.shape[-1])
+    n, ctx = cand.shape
+    if n != base.shape[0] * rho:
+        raise ValueError(f"single_edit: {n} candidates for {base.shape[0]} captions x rho = {rho}")
+    cl = host(cand_lens).reshape(-1).astype(np.int64)
+    bl = np.repeat(host(base_lens).reshape(-1).astype(np.int64), rho)
+    pfx = host(prefix).reshape(-1).astype(np.int64)
+    bad = np.nonzero(cl != bl)[0]
+    if bad.size:
+        i = int(bad[0])
+        raise ValueError(f"single_edit: candidate {i} has length {int(cl[i])}, its caption {int(bl[i])}")
+    pos = np.arange(ctx)[None, :]
+    differs = (cand != np.repeat(base, rho, axis=0)) & (pos < cl[:, None]) & (pos != pfx[:, None])
+    bad = np.nonzero(differs.any(-1))[0]
+    if bad.size:
+        i = int(bad[0])
+        j = int(differs[i].argmax())
+        raise ValueError(f"single_edit: candidate {i} differs from its caption at position {j}, not only at its prefix length {int(pfx[i])}")
+
+
 class LeafCLIPText:
     """Text tower on the HIP engine.  Not an ``nn.Module``: parameters live in ``self.flat`` (fp32, CUDA);
     ``self.params[name]`` are views into it with the OpenCLIP names."""
@@ -145,11 +174,21 @@ class LeafCLIPText:
         """Engine switches (leaf_text_set_option): 'chunk', 'last_layer_trim', 'streams' (1 | 2: two-stream
         chunk pipeline of the forward-only passes), 'normalize_fare' (training forward / backward on normalised features),
         'compact_resid' (1 default: the residual stream of the forward-only passes as the 16-bit copy + an 8-bit remainder per
-        element instead of fp32 rows; 0 = fp32 rows)."""
+        element instead of fp32 rows; 0 = fp32 rows), 'single_edit' (set per pass by the ``single_edit=`` argument of the scoring calls)."""
         if name == "ln_fold" and not value and getattr(self, "split_masks", ()):
             self.set_split_masks(())          # the split GEMMs exist in the LN-folded forward only: switching folding off switches them off
         _lib.check(self._lib.leaf_text_set_option(self._h, name.encode(), int(value)), "leaf_text_set_option")
         return self
+
+    def _single_edit_call(self, on: bool, fn):
+        """``fn()`` with the engine's per-pass ``single_edit`` option set for its duration."""
+        if not on:
+            return fn()
+        self.set_option("single_edit", 1)
+        try:
+            return fn()
+        finally:
+            self.set_option("single_edit", 0)
 
     # ------------------------------------------------------------------ nn.Module look-alikes
     def eval(self):
@@ -413,16 +452,25 @@ class LeafCLIPText:
                                                   C.c_void_p(lens.ctypes.data), _ptr(cu_dev), n, _ptr(out), 0,
                                                   _ptr(kvbuf), kvbuf.numel(), _ptr(ws), ws.numel(), self._stream()),
                    "leaf_text_forward_kv")
-        cache = {"kv": kvbuf, "base_cu": cu_dev, "base_rows": int(cu[-1]), "lens": lens, "n": n, "arith": self.arithmetic_tag()}
+        # q0: layer 0 holds the captions' Q rows too (this pass writes whole q|k|v rows) -- what a single_edit pass reads
+        cache = {"kv": kvbuf, "base_cu": cu_dev, "base_rows": int(cu[-1]), "lens": lens, "n": n, "arith": self.arithmetic_tag(),
+                 "q0": True, "tokens": t}
         return (cache, out) if want_features else cache
 
     def score_candidates(self, tokens, anchor: torch.Tensor, rho: int, objective: str = "l2", want_features=True,
-                         want_loss=False, seq_lens=None, prefix_lens=None, kv=None):
+                         want_loss=False, seq_lens=None, prefix_lens=None, kv=None, single_edit: bool = False):
         """``prefix_lens`` (host int array [B*rho], number of leading positions equal to the clean caption) together
         with ``kv`` (from ``encode_text_kv`` of the clean captions) enables prefix reuse: only positions from the
-        first changed token on are recomputed.  ``seq_lens`` must then be the candidates' full lengths."""
+        first changed token on are recomputed.  ``seq_lens`` must then be the candidates' full lengths.
+
+        ``single_edit`` (with prefix reuse only; off by default): the caller promises that every candidate is its caption with ONE
+        token replaced, at position ``prefix_lens[i]`` -- equal lengths, equal tokens behind that position.  Block 0 then projects
+        one q|k|v row per candidate instead of all of its rows (include/leaf_hip.h, "single-edit passes"); same bits.  Meant for
+        token-level substitutions (``leaf_amd.step.search_synthetic``); NOT for the string search of ``leaf_amd.attacks`` /
+        ``charmer``, where a character edit re-tokenises the rest of the caption.  ``LEAF_VERIFY_SINGLE_EDIT=1`` checks the promise
+        against the tokens (a device-to-host copy)."""
         if prefix_lens is not None and kv is not None and self.trim_rows:
-            return self._score_prefix(tokens, anchor, rho, objective, want_features, want_loss, seq_lens, prefix_lens, kv)
+            return self._score_prefix(tokens, anchor, rho, objective, want_features, want_loss, seq_lens, prefix_lens, kv, single_edit)
         """tokens [B*rho, ctx] (or [B,rho,ctx]); anchor [B,D] fp32 CUDA.  Returns (best_idx int32[B],
         best_feat [B,D] or None) (+ loss [B,rho] when want_loss)."""
         if not self._packed:
@@ -446,11 +494,12 @@ class LeafCLIPText:
                    "leaf_score_candidates")
         return (idx, feat, loss) if want_loss else (idx, feat)
 
-    def _score_prefix(self, tokens, anchor, rho, objective, want_features, want_loss, seq_lens, prefix_lens, kv):
+    def _score_prefix(self, tokens, anchor, rho, objective, want_features, want_loss, seq_lens, prefix_lens, kv, single_edit=False):
         return self.score_candidates_run(
-            self.score_candidates_prepare(tokens, anchor, rho, objective, want_features, want_loss, seq_lens, kv), prefix_lens)
+            self.score_candidates_prepare(tokens, anchor, rho, objective, want_features, want_loss, seq_lens, kv, single_edit), prefix_lens)
 
-    def score_candidates_prepare(self, tokens, anchor, rho, objective="l2", want_features=True, want_loss=False, seq_lens=None, kv=None):
+    def score_candidates_prepare(self, tokens, anchor, rho, objective="l2", want_features=True, want_loss=False, seq_lens=None, kv=None,
+                                 single_edit: bool = False):
         """Everything of a prefix-reuse ``score_candidates`` call that does NOT depend on the prefix lengths: token / anchor placement,
         output buffers, the length limits and a pinned staging buffer for the row plan.  The search calls this BEFORE it waits for the
         previous stage's winners and ``score_candidates_run(plan, prefix_lens)`` right after them: the device idles at that boundary
@@ -475,13 +524,20 @@ class LeafCLIPText:
         if kv.get("arith", self.arithmetic_tag()) != self.arithmetic_tag():
             raise ValueError(f"K/V cache built under arithmetic {kv['arith']} (compact_resid, split masks), "
                              f"the model now runs {self.arithmetic_tag()}: rebuild the cache (encode_text_kv)")
+        if single_edit:
+            # the pass reads the captions' Q rows of layer 0 and, behind the edit, as many cache rows as the candidate is long
+            if not kv.get("q0"):
+                raise ValueError("single_edit pass on a K/V cache without the captions' layer-0 Q rows (written by a fused first stage "
+                                 "that did not run with single_edit): rebuild it with encode_text_kv or score_candidates_fused(single_edit=True)")
+            if not np.array_equal(full, np.repeat(kv["lens"].astype(np.int32), rho)):
+                raise ValueError("single_edit pass: a candidate's length differs from its caption's")
         anchor = anchor.to(device=self.device, dtype=torch.float32).contiguous()
         idx = torch.empty(B, dtype=torch.int32, device=self.device)
         feat = torch.empty(B, self.cfg.embed_dim, dtype=torch.float32, device=self.device) if want_features else None
         loss = torch.empty(B, rho, dtype=torch.float32, device=self.device) if want_loss else None
         return {"full": full, "limit": limit, "host": host, "t": t, "anchor": anchor, "idx": idx, "feat": feat, "loss": loss, "B": B,
                 "rho": rho, "obj": _OBJ[objective], "kv": kv, "ws": self._workspace(1, B * rho), "max_len": int(full.max()),
-                "want_loss": want_loss}
+                "want_loss": want_loss, "single_edit": bool(single_edit)}
 
     def score_candidates_run(self, plan, prefix_lens):
         """The prefix-dependent rest of ``score_candidates_prepare``: row plan (suffix rows per candidate, their running sum), one
@@ -496,19 +552,26 @@ class LeafCLIPText:
         dev = plan["host"].to(self.device, non_blocking=True)
         cu_dev, pfx_dev = dev[:n + 1], dev[n + 1:]
         self.rows_scored += int(hv[n])
-        _lib.check(self._lib.leaf_score_candidates_prefix(
+        single_edit = plan.get("single_edit", False)
+        if single_edit and os.environ.get("LEAF_VERIFY_SINGLE_EDIT") == "1":
+            if kv.get("tokens") is None:
+                raise ValueError("LEAF_VERIFY_SINGLE_EDIT: the K/V cache does not carry its captions' tokens")
+            verify_single_edit(plan["t"], full, pfx, kv["tokens"], kv["lens"], plan["rho"])
+        self._single_edit_call(single_edit, lambda: _lib.check(self._lib.leaf_score_candidates_prefix(
             self._h, _ptr(self.flat), _ptr(self.w16), _ptr(plan["t"]), C.c_void_p(suf.ctypes.data), _ptr(cu_dev), _ptr(pfx_dev),
             _ptr(kv["base_cu"]), _ptr(kv["kv"]), kv["base_rows"], plan["max_len"], _ptr(plan["anchor"]), plan["B"], plan["rho"], plan["obj"],
             _ptr(plan["idx"]), _ptr(plan["feat"]), _ptr(plan["loss"]), _ptr(plan["ws"]), plan["ws"].numel(), self._stream()),
-            "leaf_score_candidates_prefix")
+            "leaf_score_candidates_prefix"))
         return (plan["idx"], plan["feat"], plan["loss"]) if plan["want_loss"] else (plan["idx"], plan["feat"])
 
     def score_candidates_fused(self, base_tokens, base_lens, tokens, anchor: torch.Tensor, rho: int, seq_lens, prefix_lens,
-                               objective: str = "l2", want_features: bool = False, want_loss: bool = False):
+                               objective: str = "l2", want_features: bool = False, want_loss: bool = False, single_edit: bool = False):
         """``encode_text_kv(base_tokens)`` and the first stage's ``score_candidates(..., prefix_lens, kv)`` in ONE pass
         (leaf_score_candidates_prefix_fused: the B clean captions ride in the launches of their B*rho candidates).
         Returns (best_idx, best_feat or None, kv cache for the later stages[, loss [B, rho] when want_loss]), or None when
-        the rows do not fit one chunk (the caller then uses the two separate calls).  Bit-identical to the separate calls."""
+        the rows do not fit one chunk (the caller then uses the two separate calls).  Bit-identical to the separate calls.
+        ``single_edit``: as in ``score_candidates``; the cache it returns then holds the captions' layer-0 Q rows, which the later
+        single_edit stages read (a cache of a pass without it does not, and such a stage refuses it)."""
         if not self._packed:
             self.pack()
         B = anchor.shape[0]
@@ -526,6 +589,11 @@ class LeafCLIPText:
         ct = self._tokens(tokens.reshape(-1, tokens.shape[-1]))
         if bt.shape[0] != B or ct.shape[0] != B * rho:
             raise ValueError("captions / candidate rows do not match B, B*rho")
+        if single_edit:
+            if not np.array_equal(full, np.repeat(blens.astype(np.int64), rho)):
+                raise ValueError("single_edit pass: a candidate's length differs from its caption's")
+            if os.environ.get("LEAF_VERIFY_SINGLE_EDIT") == "1":
+                verify_single_edit(ct, full, pfx, bt, blens, rho)
         t = torch.cat([bt, ct], 0)
         base_rows = int(cu[B])
         need = base_rows * 3 * self.cfg.width * 2 * self.cfg.layers
@@ -539,15 +607,17 @@ class LeafCLIPText:
         loss = torch.empty(B, rho, dtype=torch.float32, device=self.device) if want_loss else None
         ws = self._workspace(1, B + B * rho)
         max_len = int(max(int(full.max()), int(blens.max())))
-        rc = self._lib.leaf_score_candidates_prefix_fused(
+        rc = self._single_edit_call(single_edit, lambda: self._lib.leaf_score_candidates_prefix_fused(
             self._h, _ptr(self.flat), _ptr(self.w16), _ptr(t), C.c_void_p(lens.ctypes.data), _ptr(cu_dev), _ptr(pfx_dev), max_len,
             _ptr(anchor), B, rho, _OBJ[objective], _ptr(idx), _ptr(feat), _ptr(loss), _ptr(self._kv), self._kv.numel(),
-            _ptr(ws), ws.numel(), self._stream())
+            _ptr(ws), ws.numel(), self._stream()))
         if rc == 2:
             return None
         _lib.check(rc, "leaf_score_candidates_prefix_fused")
         self.rows_scored += int(cu[-1])
-        cache = {"kv": self._kv, "base_cu": cu_dev[:B + 1], "base_rows": base_rows, "lens": blens, "n": B, "arith": self.arithmetic_tag()}
+        # q0: without single_edit the fused launch keeps the captions' Q rows on chip, layer 0 of the cache holds K and V only
+        cache = {"kv": self._kv, "base_cu": cu_dev[:B + 1], "base_rows": base_rows, "lens": blens, "n": B, "arith": self.arithmetic_tag(),
+                 "q0": bool(single_edit), "tokens": bt}
         return (idx, feat, cache, loss) if want_loss else (idx, feat, cache)
 
     # ------------------------------------------------------------------ training

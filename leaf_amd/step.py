@@ -113,6 +113,10 @@ def search_synthetic(model, anchor: torch.Tensor, base: torch.Tensor, cfg: StepC
     B = base.shape[0]
     ar = torch.arange(B, device=base.device)
     fuse = reuse and os.environ.get("LEAF_FUSE_KV", "1") != "0"
+    # SyntheticCandidates builds single-token substitutions by construction in both stages (same length, one id replaced at the
+    # position that is the prefix length): block 0 projects one q|k|v row per candidate (LeafCLIPText.score_candidates,
+    # ``single_edit``).  LEAF_SINGLE_EDIT=0 restores the full projection (the A/B arm).
+    single = reuse and os.environ.get("LEAF_SINGLE_EDIT", "1") != "0"
     for _ in range(cfg.k_adv):
         cand, pos = gen.stage1(cur)
         if anchor_ready is not None:
@@ -121,24 +125,27 @@ def search_synthetic(model, anchor: torch.Tensor, base: torch.Tensor, cfg: StepC
         # stage 1 with the clean captions' K/V pass fused in (their rows ride in the candidates' launches); falls back to the
         # separate pass when the rows do not fit one chunk
         fused = model.score_candidates_fused(cur, base_lens, cand.view(B * cfg.rho, -1), anchor, cfg.rho, cand_lens,
-                                             pos.reshape(-1)) if fuse else None
+                                             pos.reshape(-1), single_edit=single) if fuse else None
         if fused is not None:
             best1, _, kv = fused
         else:
             kv = model.encode_text_kv(cur, seq_lens=base_lens) if reuse else None
             best1, _ = model.score_candidates(cand.view(B * cfg.rho, -1), anchor, cfg.rho, "l2", want_features=False,
-                                              seq_lens=cand_lens, prefix_lens=pos.reshape(-1) if reuse else None, kv=kv)
+                                              seq_lens=cand_lens, prefix_lens=pos.reshape(-1) if reuse else None, kv=kv, single_edit=single)
         cand = gen.stage2_device(cur, best1)                             # queued behind stage 1, before the host waits
         # ... and everything of the second stage's call that does not need the winners (the device has nothing to run between their
         # arrival on the host and that call's first launch)
+        # (the second stage looks block 0's rows up only in a cache that holds the captions' layer-0 Q rows: one written by a first
+        # stage that ran with the option, or by encode_text_kv)
+        single2 = single and kv is not None and bool(kv.get("q0"))
         plan2 = model.score_candidates_prepare(cand.view(B * cfg.rho, -1), anchor, cfg.rho, "l2", want_features=False,
-                                               seq_lens=cand_lens, kv=kv) if reuse and kv is not None else None
+                                               seq_lens=cand_lens, kv=kv, single_edit=single2) if reuse and kv is not None else None
         pos2 = gen.stage2_positions(pos, best1.cpu().numpy())           # the search's device->host sync (B indices)
         if plan2 is not None:
             best2, _ = model.score_candidates_run(plan2, pos2)
         else:
             best2, _ = model.score_candidates(cand.view(B * cfg.rho, -1), anchor, cfg.rho, "l2", want_features=False,
-                                              seq_lens=cand_lens, prefix_lens=pos2.reshape(-1) if reuse else None, kv=kv)
+                                              seq_lens=cand_lens, prefix_lens=pos2.reshape(-1) if reuse else None, kv=kv, single_edit=single2)
         cur = cand[ar, best2.to(torch.int64)]
     return cur
 
