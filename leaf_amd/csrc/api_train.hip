@@ -112,13 +112,19 @@ extern "C" int leaf_text_forward_train_delta(leaf_text_t h, const float* P, cons
         uint16_t* xn1 = st.xn1 + l * rd; uint16_t* qkv = st.qkv + 3 * l * rd; uint16_t* ao = st.ao + l * rd;
         uint16_t* xn2 = st.xn2 + l * rd; uint16_t* pre = st.pre + 4 * l * rd; uint16_t* hh = st.hh + 4 * l * rd;
         if (l > 0) LEAF_TRY(leaf_launch_layernorm(xin, P + o.ln1_w, P + o.ln1_b, cf.ln_eps, xn1, rows, d, dt, s));
-        if (leaf_gemm(dt, EPI_STORE_T, xn1, d, W + h->w16_qkv(l), d, qkv, 3 * d, P + o.qkv_b, nullptr, rows, 3 * d, d, 0, s)) return 1;
+        if (leaf_gemm(gemm_dense(xn1, W + h->w16_qkv(l), qkv, P + o.qkv_b, rows, 3 * d, d), dt, EPI_STORE_T, s)) return 1;
         LEAF_TRY(leaf_launch_attention_fwd(qkv, nullptr, ao, n_seq, map, cf.heads, d, dt, s, nullptr, max_len));
         // out-of-place residual adds (aux = residual source): the stash keeps xin, x1 and xout
-        if (leaf_gemm(dt, EPI_RESID_F32, ao, d, W + h->w16_out(l), d, x1, d, P + o.out_b, xin, rows, d, d, 0, s)) return 1;
+        GemmArgs g = gemm_dense(ao, W + h->w16_out(l), x1, P + o.out_b, rows, d, d);
+        g.aux = xin;
+        if (leaf_gemm(g, dt, EPI_RESID_F32, s)) return 1;
         LEAF_TRY(leaf_launch_layernorm(x1, P + o.ln2_w, P + o.ln2_b, cf.ln_eps, xn2, rows, d, dt, s));
-        if (leaf_gemm(dt, EPI_ACT_T, xn2, d, W + h->w16_fc(l), d, hh, 4 * d, P + o.fc_b, pre, rows, 4 * d, d, cf.activation, s)) return 1;
-        if (leaf_gemm(dt, EPI_RESID_F32, hh, 4 * d, W + h->w16_proj(l), 4 * d, xout, d, P + o.proj_b, x1, rows, d, 4 * d, 0, s)) return 1;
+        g = gemm_dense(xn2, W + h->w16_fc(l), hh, P + o.fc_b, rows, 4 * d, d);
+        g.aux = pre; g.act = cf.activation;
+        if (leaf_gemm(g, dt, EPI_ACT_T, s)) return 1;
+        g = gemm_dense(hh, W + h->w16_proj(l), xout, P + o.proj_b, rows, d, 4 * d);
+        g.aux = x1;
+        if (leaf_gemm(g, dt, EPI_RESID_F32, s)) return 1;
     }
     if (leaf_project_rows_ok(d, cf.embed_dim) && ws && ws_bytes >= (size_t)n_seq * d * 4) {
         // pooled rows -> ws, ln_final -> st.pooled (the stash the backward reads), fp32 matrix-core projection -> out
@@ -187,14 +193,14 @@ static int backward_impl(leaf_text_t h, const float* P, const void* w16_bwd, con
         const uint16_t* xn1 = st.xn1 + l * rd; const uint16_t* qkv = st.qkv + 3 * l * rd; const uint16_t* ao = st.ao + l * rd;
         const uint16_t* xn2 = st.xn2 + l * rd; const uint16_t* pre = st.pre + 4 * l * rd; const uint16_t* hh = st.hh + 4 * l * rd;
         // ---- MLP
-        if (leaf_gemm(gk, EPI_ACTGRAD_T, b.dx16, d, WT + h->w16_proj(l), d, b.big16, 4 * d, nullptr, (void*)pre, rows,
-                 4 * d, d, cf.activation, s, 0.f, fk)) return 1;
-        if (leaf_gemm(gk, EPI_STORE_F32, b.big16, 4 * d, WT + h->w16_fc(l), 4 * d, b.dxn, d, nullptr, nullptr, rows, d,
-                 4 * d, 0, s)) return 1;
+        GemmArgs g = gemm_dense(b.dx16, WT + h->w16_proj(l), b.big16, nullptr, rows, 4 * d, d);
+        g.aux = (void*)pre; g.aux_f16 = fk; g.act = cf.activation;
+        if (leaf_gemm(g, gk, EPI_ACTGRAD_T, s)) return 1;
+        if (leaf_gemm(gemm_dense(b.big16, WT + h->w16_fc(l), b.dxn, nullptr, rows, d, 4 * d), gk, EPI_STORE_F32, s)) return 1;
         LEAF_TRY(leaf_launch_layernorm_bwd(b.dxn, x1, P + o.ln2_w, cf.ln_eps, b.dx, b.dx16b, gk,
                                            G ? b.lnpart + (size_t)(2 * l + 1) * ln_stride : nullptr, rows, d, s));
         // ---- attention
-        if (leaf_gemm(gk, EPI_STORE_T, b.dx16b, d, WT + h->w16_out(l), d, b.do16, d, nullptr, nullptr, rows, d, d, 0, s)) return 1;
+        if (leaf_gemm(gemm_dense(b.dx16b, WT + h->w16_out(l), b.do16, nullptr, rows, d, d), gk, EPI_STORE_T, s)) return 1;
         LEAF_TRY(leaf_launch_attention_bwd(qkv, h->fwd_dtype, b.do16, b.dqkv, gk, n_seq, map, cf.heads, d, s));
         if (G) {
             // all four weight + bias gradients of the block in one launch (wgrad.hip); must run before ln1's backward
@@ -217,8 +223,7 @@ static int backward_impl(leaf_text_t h, const float* P, const void* w16_bwd, con
             // element 0 before another rank's poison exists (tests/test_dp_gloo.py pins both facts)
             LEAF_TRY(leaf_launch_sat_check16(bufs, numel, 5, h->scaler, G + h->tok_emb, s));
         }
-        if (leaf_gemm(gk, EPI_STORE_F32, b.dqkv, 3 * d, WT + h->w16_qkv(l), 3 * d, b.dxn, d, nullptr, nullptr, rows, d,
-                 3 * d, 0, s)) return 1;
+        if (leaf_gemm(gemm_dense(b.dqkv, WT + h->w16_qkv(l), b.dxn, nullptr, rows, d, 3 * d), gk, EPI_STORE_F32, s)) return 1;
         LEAF_TRY(leaf_launch_layernorm_bwd(b.dxn, xin, P + o.ln1_w, cf.ln_eps, b.dx, b.dx16, gk,
                                            G ? b.lnpart + (size_t)(2 * l) * ln_stride : nullptr, rows, d, s));
         // every gradient of block l is final here: the caller may start reducing this block's bucket (step.py)

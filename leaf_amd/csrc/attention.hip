@@ -60,7 +60,7 @@ __device__ __forceinline__ s16x4 load_vt_frag(const char* vlds, int key0, int di
     }
 }
 
-// EDIT (single-edit scoring passes, block 0; api.hip): a sequence's q|k|v rows are not computed but looked up.  qkv is then a
+// EDIT (single-edit scoring passes, block 0; forward.hip attention_stage): a sequence's q|k|v rows are not computed but looked up.  qkv is then a
 // [sequences of the launch, 3d] table with ONE row per sequence -- the row of its edited position (= its prefix length) -- and
 // every other position, before AND behind the edit, reads the clean caption's row from kv_base (all three thirds, Q included).
 // Sequences in front of map.group_off are the captions themselves: cache rows only.  Same body, same bits.

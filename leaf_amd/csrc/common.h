@@ -85,7 +85,7 @@ __device__ __forceinline__ void unpack4(uint2 u, float (&o)[4]) {
     for (int i = 0; i < 4; ++i) o[i] = TT::to_f32(v[i]);
 }
 
-// ---- Residual stream of the forward-only passes in 16 + 8 bits (api.hip "compact residual").  A residual value x is kept as
+// ---- Residual stream of the forward-only passes in 16 + 8 bits (forward.hip: FwdPass::lo8, residual_add).  A residual value x is kept as
 // hi = the 16-bit copy the next GEMM multiplies anyway (x16) and lo8 = its remainder x - hi (exact in fp32, at most half an ulp of
 // hi) as an fp8 e4m3 number in a BLOCK-SCALED format: the four values a lane holds (4 consecutive columns) share one power-of-two
 // scale -- the exponent of the largest |hi| among them, at least fp16's smallest normal -- and CDNA4's MX conversions do the rest:

@@ -128,7 +128,7 @@ __global__ __launch_bounds__(256) void embed_fold_kernel(const float* __restrict
             if constexpr (LO8) *(unsigned*)((unsigned char*)x_out + (size_t)row * d + 4 * c) = resid_lo4<TT>(v.x, v.y, v.z, v.w, hi);
             else *(float4*)(xo + 4 * c) = v;
             *(uint2*)(x16 + (size_t)row * d + 4 * c) = hi;
-            if (split3) {       // [hi | lo | hi] of the exact fp32 row: the A operand of block 0's three-pass QKV GEMM (api.hip, split blocks)
+            if (split3) {       // [hi | lo | hi] of the exact fp32 row: the A operand of block 0's three-pass QKV GEMM (forward.hip embed, split blocks)
                 float hf[4];
                 unpack4<TT>(hi, hf);
                 const uint2 lo = pack4<TT>(v.x - hf[0], v.y - hf[1], v.z - hf[2], v.w - hf[3]);
@@ -624,7 +624,7 @@ hipError_t leaf_launch_copy_bytes(const void* src, void* dst, size_t bytes, hipS
     return hipGetLastError();
 }
 
-// out[i] = i: the row offsets of a RowMap with one row per sequence (api.hip, the fresh rows of a single-edit pass)
+// out[i] = i: the row offsets of a RowMap with one row per sequence (forward.hip embed_fresh_rows: the fresh rows of a single-edit pass)
 namespace {
 __global__ __launch_bounds__(256) void iota_kernel(int32_t* __restrict__ out, int n) {
     leaf_fp16_sat_mode();

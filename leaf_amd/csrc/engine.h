@@ -1,4 +1,5 @@
-// Host-side handle shared by api.hip (inference / scoring) and api_train.hip (training step).
+// Host-side handle shared by api.hip (C ABI: handle, packing, scoring), forward.hip (forward-only pass driver) and api_train.hip
+// (training step).
 #pragma once
 #include <string>
 #include <vector>
@@ -25,7 +26,7 @@ struct leaf_text {
     int grad_dtype;  // 16-bit type of the gradient path: LEAF_F16 (loss-scaled, default) or LEAF_BF16
     int normalize_fare = 0;   // --normalize_fare: the training forward returns F.normalize(features), the backward follows
     float* scaler = nullptr;  // gradient-scaler state (device, leaf_hip.h LEAF_SC_*) or null: no saturation check, no back-off
-    // Two-stream chunk pipeline of the forward-only passes (api.hip forward_all): sequence chunks alternate between the
+    // Two-stream chunk pipeline of the forward-only passes (forward.hip forward_all): sequence chunks alternate between the
     // caller's stream and a side stream owned by the handle, so one chunk's HBM-bound kernels (LN, attention, the
     // residual epilogues) and grid tails overlap the other chunk's MFMA-bound K loops.  Measured: kernels of the two
     // streams do run concurrently, but the search pass is no faster (57.4 vs 56.0 ms), so the default is streams = 1.
@@ -36,7 +37,7 @@ struct leaf_text {
     int fuse_attn = 1;
     // Single-edit scoring passes (option 'single_edit', include/leaf_hip.h): the caller promises that every candidate of the pass is
     // its caption with ONE token replaced at position prefix[i].  Block 0's q|k|v row depends on (token, position) alone, so only
-    // that one row per candidate is projected; every other row is read from layer 0 of the captions' cache (api.hip forward_chunk).
+    // that one row per candidate is projected; every other row is read from layer 0 of the captions' cache (forward.hip: embed_fresh_rows, attention_stage).
     int single_edit = 0;
     static constexpr int PLAN_RING = 8;
     int32_t* plan_host[PLAN_RING] = {};
@@ -103,20 +104,17 @@ struct leaf_text {
 };
 
 size_t leaf_train_ws_bytes(const leaf_text* h, int n_seq);  // api_train.hip
-// GEMM launch shared by both API files; when the profiler is armed (leaf_prof_begin) each launch is bracketed
-// by HIP events on its own stream and accounted under its epilogue id.
-// LN folding operands of leaf_gemm (EPI_LNFOLD_* consume rowstat / ln_s, EPI_RESID_LN produces x16 / stat_out)
-struct GemmLn {
-    const float* ln_s = nullptr;
-    const float2* rowstat = nullptr;
-    float2* stat_out = nullptr;
-    void* x16 = nullptr;
-    int stat_ld = 0, ldx16 = 0;
-    float eps = 1e-5f;
-};
-int leaf_gemm(int dtype, int epi, const void* A, int lda, const void* B, int ldb, void* C, int ldc, const float* bias,
-              void* aux, int M, int N, int K, int act, hipStream_t s, float beta = 0.f, int aux_f16 = 0,
-              const float* alpha = nullptr, const GemmLn* ln = nullptr, int a_wrap = 0);
+// GEMM launch shared by the host files (api.hip): checks the operands of the LN epilogues (EPI_LNFOLD_* consume rowstat / ln_s /
+// bias, EPI_RESID_LN* produce x16 / stat_out); when the profiler is armed (leaf_prof_begin) each launch is bracketed by HIP
+// events on its own stream and accounted under its epilogue id.
+int leaf_gemm(const GemmArgs& g, int dtype, int epi, hipStream_t s);
+// C[M,N] (+)= A[M,K] B[N,K]^T + bias on densely stored operands; everything optional stays at GemmArgs' defaults
+inline GemmArgs gemm_dense(const void* A, const void* B, void* C, const float* bias, int M, int N, int K) {
+    GemmArgs g;
+    g.A = A; g.B = B; g.C = C; g.bias = bias;
+    g.M = M; g.N = N; g.K = K; g.lda = K; g.ldb = K; g.ldc = N;
+    return g;
+}
 int leaf_qkv_attn(const QkvAttnArgs& a, int dtype, hipStream_t s);   // leaf_launch_qkv_attn + profiler accounting
 void leaf_set_error(const char* fmt, ...);
 int leaf_check(hipError_t e, const char* what);
@@ -141,3 +139,63 @@ struct Carver {
     }
     bool ok() const { return off <= cap; }
 };
+
+// ------------------------------------------------------------------ forward-only pass driver (forward.hip)
+struct FwdBuf {    // workspace of one chunk
+    float* x;      // [rows,d] fp32 residual stream (16 + 8-bit stream: the [rows,d] remainder bytes)
+    uint16_t* a;   // [rows,d]   LN output / attention output (aliased)
+    uint16_t* qkv; // [rows,3d]
+    uint16_t* hh;  // [rows,4d]
+    int32_t* eot;  // [seqs] pooled position per sequence (last-layer trimming)
+    uint16_t* x16; // [rows,d]   LN folding: 16-bit copy of the residual stream (A operand of the QKV / c_fc GEMMs)
+    float2* stat;  // [d/64][rows] LN folding: (sum, M2) per row and 64-column group
+    float2* rowstat; // [rows]     LN folding: (mean, rstd) per row
+    int32_t* tile_seq; // [seqs + 1][2] fused QKV + attention: (first sequence, first row) of every M tile (a sequence has >= 1 row)
+};
+FwdBuf carve_fwd(const leaf_text* h, Carver& c, int cs);   // cs sequences of context_length rows
+size_t fwd_chunk_bytes(const leaf_text* h, int cs);        // what carve_fwd takes
+
+// who produces and who reads the per-layer q|k|v cache of the clean captions (stride kv_stride elements per layer)
+struct KvPlan {
+    uint16_t* kv_write = nullptr;       // the rows of this (single) chunk are produced INTO the cache (leaf_text_forward_kv)
+    const uint16_t* kv_read = nullptr;  // prefix mode: attention reads the prefix K/V of layer l from kv_read + l * kv_stride
+    size_t kv_stride = 0;
+    // fused pass (leaf_score_candidates_prefix_fused): the clean captions are the FIRST kv_self_rows rows of this chunk; the
+    // candidates' attention reads their K/V from the chunk's own rows, and every layer's caption rows also go to kv_copy
+    uint16_t* kv_copy = nullptr;
+    size_t kv_self_rows = 0;
+    // fused QKV + attention launches (qkv_attn.hip): number of M tiles cut for this chunk (FwdBuf::tile_seq holds them); 0 = two kernels
+    int attn_tiles = 0;
+    int attn_max_len = 0;     // longest sequence (prefix + computed rows) the plan was cut for: sizes the caption images
+};
+// the layer stack on one chunk of `cs` sequences (`rows` = their packed row count); features -> out [cs, D], or out == null:
+// K/V-only pass.  max_len: longest sequence (prefix + computed rows); 0 = context_length
+int forward_chunk(const leaf_text* h, const float* P, const uint16_t* W, const int32_t* tokens, int cs, int rows, RowMap map,
+                  float* out, int normalize, const FwdBuf& b, hipStream_t s, const KvPlan& kv, int max_len);
+
+struct PrefixPlan {   // prefix reuse: see RowMap in common.h
+    const int32_t* prefix_dev = nullptr;
+    const int32_t* base_cu_dev = nullptr;
+    const uint16_t* kv = nullptr;
+    size_t kv_stride = 0;
+    int group = 1;
+    int max_len = 0;   // upper bound of prefix + suffix length over the candidates (0 = context_length)
+    int group_off = 0;          // fused pass: the first group_off sequences are the clean captions
+    uint16_t* kv_copy = nullptr;
+    size_t kv_self_rows = 0;
+};
+// all sequences of a pass, in chunks bounded by a row budget; carves one FwdBuf per stream from `c`
+int forward_all(leaf_text* h, const float* P, const void* W, const int32_t* tokens, const int32_t* lens, const int32_t* cu_dev,
+                int n_seq, float* out, int normalize, Carver& c, hipStream_t s, const PrefixPlan& pp = PrefixPlan());
+
+// operands of a block's QKV product C = A[M, K] B[3d, K]^T: the LN-folded form reads ln_s and bias = c, the plain one bias alone
+struct QkvOperands {
+    const void* A;
+    const uint16_t* B;
+    const float* ln_s;
+    const float* bias;
+    int K;
+};
+// arguments of the fused QKV + attention launch over `M` rows / `n_seq` sequences cut into `n_tiles` M tiles for `max_len`
+QkvAttnArgs fill_qkv_attn_args(const QkvOperands& q, const float2* rowstat, void* out, const void* kv_base, const int32_t* eot_pos,
+                               const int32_t* tile_seq, const RowMap& map, int M, int n_seq, int n_tiles, int heads, int d, int max_len);

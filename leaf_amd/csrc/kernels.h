@@ -1,4 +1,4 @@
-// Internal launcher interface between the C-ABI layer (api.hip) and the kernel files.
+// Internal launcher interface between the host layer (api.hip, forward.hip, api_train.hip) and the kernel files.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -30,32 +30,32 @@ enum {
 #define LEAF_PROF_BIG 1024     // added to the key of launches of >= 16,384 rows (leaf_prof_end_shapes)
 
 
+// `GemmArgs g;` is a launch with nothing optional: a caller fills the operands and shapes and the few other fields it means
 struct GemmArgs {
-    const void* A;  // [M,K] 16-bit, row stride lda (elements)
-    const void* B;  // [N,K] 16-bit, row stride ldb
-    void* C;        // [M,N] 16-bit or fp32, row stride ldc
-    const float* bias;  // [N] or null
-    void* aux;          // see EPI_*
-    int M, N, K, lda, ldb, ldc;
-    int act;      // ACT_GELU / ACT_QUICKGELU
-    int aux_f16;  // EPI_ACTGRAD_T: aux is fp16 (1) or bf16 (0)
-    float beta;
-    void* stamps; // diagnostic builds only (-DLEAF_GEMM_STAMPS)
-    const float* alpha;  // optional DEVICE scalar multiplying the accumulator (gradient un-scaling), or null
-    int ngroup;   // tile order of the 256^2 kernels: N tiles per group (0 = all: M-major / N-minor over the whole matrix)
+    const void* A = nullptr;  // [M,K] 16-bit, row stride lda (elements)
+    const void* B = nullptr;  // [N,K] 16-bit, row stride ldb
+    void* C = nullptr;        // [M,N] 16-bit or fp32, row stride ldc
+    const float* bias = nullptr;  // [N] or null
+    void* aux = nullptr;          // see EPI_*
+    int M = 0, N = 0, K = 0, lda = 0, ldb = 0, ldc = 0;
+    int act = 0;      // ACT_GELU / ACT_QUICKGELU
+    int aux_f16 = 0;  // EPI_ACTGRAD_T: aux is fp16 (1) or bf16 (0)
+    float beta = 0.f;
+    void* stamps = nullptr; // diagnostic builds only (-DLEAF_GEMM_STAMPS)
+    const float* alpha = nullptr;  // optional DEVICE scalar multiplying the accumulator (gradient un-scaling), or null
+    int ngroup = 0;   // tile order of the 256^2 kernels: N tiles per group (0 = all: M-major / N-minor over the whole matrix)
     // LayerNorm folding (EPI_LNFOLD_* read rowstat / ln_s, EPI_RESID_LN writes x16 / stat_out); the partial statistics are
     // laid out [64-column group][row] with row stride stat_ld, one (sum, M2) pair per (group, row)
-    const float* ln_s;        // [N] row sums of the gamma-scaled 16-bit weights
-    const float2* rowstat;    // [M] (mean, rstd) of the A rows (leaf_launch_ln_finalize of the producer's partials)
-    float2* stat_out;         // [N / 64][stat_ld]
-    void* x16;                // [M, N] 16-bit copy of the fp32 output, row stride ldx16
-    int stat_ld, ldx16;
-    float ln_eps;
-    int stagger;  // unused (a retired GEMM experiment's start delay); kept so that the kernels' argument layout does not change
+    const float* ln_s = nullptr;        // [N] row sums of the gamma-scaled 16-bit weights
+    const float2* rowstat = nullptr;    // [M] (mean, rstd) of the A rows (leaf_launch_ln_finalize of the producer's partials)
+    float2* stat_out = nullptr;         // [N / 64][stat_ld]
+    void* x16 = nullptr;                // [M, N] 16-bit copy of the fp32 output, row stride ldx16
+    int stat_ld = 0, ldx16 = 0;
+    float ln_eps = 0.f;
     // A operand re-read along K (gemm256h.hip only; leaf_launch_gemm refuses it elsewhere): after a_wrap K tiles of 64 the A panel's k
     // offset restarts at 0, i.e. the kernel multiplies [A | A | ...] [M, K] against B [N, K] with A stored ONCE as [M, 64 a_wrap].
-    // 0 = off.  The out-projection of a split block: [A | A] x [W_hi | W_lo]^T in one launch (api.hip).
-    int a_wrap;
+    // 0 = off.  The out-projection of a split block: [A | A] x [W_hi | W_lo]^T in one launch (forward.hip residual_add).
+    int a_wrap = 0;
 };
 
 hipError_t leaf_launch_gemm(const GemmArgs& p, int dtype, int epi, hipStream_t s);
@@ -74,20 +74,20 @@ hipError_t leaf_launch_gemm64(const GemmArgs& p, int dtype, int epi, hipStream_t
 #define LEAF_QKVATTN_NCAP 3        // clean captions whose cached prefix K/V one M tile may need (LDS images)
 #define LEAF_QKVATTN_CAPROWS 80    // rows per caption image = longest sequence the fused kernel takes (CLIP: 77)
 struct QkvAttnArgs {
-    const void* A;            // [M, K] 16-bit copy of the residual stream (row stride lda)
-    const void* B;            // [3 d, K] gamma-scaled in_proj weights, standard [q; k; v] row order (row stride ldb)
-    const float* bias;        // [3 d] c = W . ln_beta + in_proj_bias
-    const float* ln_s;        // [3 d] row sums of B
-    const float2* rowstat;    // [M] (mean, rstd) of the A rows
-    void* out;                // attention output [M, d] 16-bit (eot_pos: [n_seq, d], one row per sequence)
-    const void* kv_base;      // this layer's cached q|k|v rows of the clean captions (row stride kv_ld), or null
-    const int32_t* eot_pos;   // last-layer mode: pooled position per sequence of the launch, or null
-    const int32_t* tile_seq;  // [n_tiles + 1][2] (first sequence, first row), launch-relative, of every M tile (leaf_qkv_attn_plan)
-    RowMap map;
-    int M, K, lda, ldb, heads, d, n_tiles, n_seq, kv_ld;
-    int hsplit;               // head groups an M range is split into across XCDs (1 = an XCD runs all heads of its tiles)
-    int ncap, caprows;        // caption images in LDS: how many, rows each (leaf_qkv_attn_lds_plan; the tile plan was cut for ncap)
-    void* stamps;             // diagnostic builds only (-DLEAF_GEMM_STAMPS)
+    const void* A = nullptr;            // [M, K] 16-bit copy of the residual stream (row stride lda)
+    const void* B = nullptr;            // [3 d, K] gamma-scaled in_proj weights, standard [q; k; v] row order (row stride ldb)
+    const float* bias = nullptr;        // [3 d] c = W . ln_beta + in_proj_bias
+    const float* ln_s = nullptr;        // [3 d] row sums of B
+    const float2* rowstat = nullptr;    // [M] (mean, rstd) of the A rows
+    void* out = nullptr;                // attention output [M, d] 16-bit (eot_pos: [n_seq, d], one row per sequence)
+    const void* kv_base = nullptr;      // this layer's cached q|k|v rows of the clean captions (row stride kv_ld), or null
+    const int32_t* eot_pos = nullptr;   // last-layer mode: pooled position per sequence of the launch, or null
+    const int32_t* tile_seq = nullptr;  // [n_tiles + 1][2] (first sequence, first row), launch-relative, of every M tile (leaf_qkv_attn_plan)
+    RowMap map = {};
+    int M = 0, K = 0, lda = 0, ldb = 0, heads = 0, d = 0, n_tiles = 0, n_seq = 0, kv_ld = 0;
+    int hsplit = 1;           // head groups an M range is split into across XCDs (1 = an XCD runs all heads of its tiles); the launcher picks
+    int ncap = 0, caprows = 0;  // caption images in LDS: how many, rows each (leaf_qkv_attn_lds_plan; the tile plan was cut for ncap)
+    void* stamps = nullptr;   // diagnostic builds only (-DLEAF_GEMM_STAMPS)
 };
 int leaf_qkv_attn_tile_rows();                       // rows of an M tile of the kernel form in use
 int leaf_qkv_attn_ncap(int max_len);                 // captions per tile for sequences of <= max_len positions (0: not taken)
