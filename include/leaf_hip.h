@@ -152,6 +152,30 @@ int leaf_score_candidates_prefix_fused(leaf_text_t h, const float* params, const
                                        const float* anchor, int B, int rho, int objective, int32_t* best_idx, float* best_feat,
                                        float* loss, void* kv, size_t kv_bytes, void* ws, size_t ws_bytes, leaf_stream_t s);
 
+/* Zero-shot classification scoring (leaf_amd/csrc/classify.hip; attack_text_charmer_classification, utils_attacks.py:582-643): the
+ * pass of leaf_score_candidates with L2-normalised features, scored against a class matrix shared by all captions instead of one
+ * anchor row per caption.  class_feat [C, embed_dim] (fp32, device, unit rows: the caller normalises), labels [B] (int32, device,
+ * each in [0, C): the caller checks, the engine cannot), LEAF_CLS_MIN_CLASSES <= C <= LEAF_CLS_MAX_CLASSES (an error outside).
+ *   logit[c] = <feat[b,r], class_feat[c]>;  loss[b,r] = max_{c != labels[b]} logit[c] - logit[labels[b]] (margin_loss_lm, :145-151;
+ *   NaN when a logit is NaN);  pred[b,r] = first arg-max of logit over c (:630-631).
+ * loss [B,rho] is REQUIRED here (best_idx is taken from it); pred (int32 [B,rho]), logits (fp32 [B*rho, C]) and best_feat may be
+ * NULL.  best_idx[b] = the first of loss[b,:] in the order of leaf_select_topk (NaN first, larger value, lower column).  A
+ * candidate's logits, loss and pred do not depend on B, rho, its place in the launch or the grouping of captions into launches:
+ * each inner product is summed in one fixed order.  leaf_score_candidates_prefix_cls: the same under prefix reuse (arguments
+ * as leaf_score_candidates_prefix); bit-identical results. */
+#define LEAF_CLS_MIN_CLASSES 2
+#define LEAF_CLS_MAX_CLASSES 1024
+int leaf_score_candidates_cls(leaf_text_t h, const float* params, const void* w16_fwd, const int32_t* tokens,
+                              const int32_t* seq_lens, const int32_t* cu_rows, const float* class_feat, int C,
+                              const int32_t* labels, int B, int rho, int32_t* best_idx, float* best_feat, float* loss,
+                              int32_t* pred, float* logits, void* ws, size_t ws_bytes, leaf_stream_t s);
+int leaf_score_candidates_prefix_cls(leaf_text_t h, const float* params, const void* w16_fwd, const int32_t* tokens,
+                                     const int32_t* suffix_lens, const int32_t* cu_suffix, const int32_t* prefix,
+                                     const int32_t* base_cu, const void* kv, size_t base_rows, int max_len,
+                                     const float* class_feat, int C, const int32_t* labels, int B, int rho, int32_t* best_idx,
+                                     float* best_feat, float* loss, int32_t* pred, float* logits, void* ws, size_t ws_bytes,
+                                     leaf_stream_t s);
+
 /* Exact work skipping, part 3 ("single-edit passes"; option "single_edit" of leaf_text_set_option, 0/1, default 0, set by the caller
  * for the passes it holds for).  Block 0's q|k|v row is LN1(E[token] + P[position]) W_qkv + b: it depends on the pair (token,
  * position) and on nothing else.  With the option set the caller PROMISES, for every candidate i of a leaf_score_candidates_prefix /
@@ -382,6 +406,9 @@ int leaf_op_qkv_attn(int dtype, const void* x16, const void* Wp, const float* c_
                      void* out, const void* kv, const int32_t* lens, const int32_t* cu, const int32_t* prefix,
                      const int32_t* base_cu, const int32_t* eot_pos, int32_t* tile_seq, int n_seq, int rows, int group,
                      int ctx, int heads, int width, leaf_stream_t s);
+/* the classification score of leaf_score_candidates_cls alone, on given feature rows feat [B*rho, D] (kernel hook for the tests) */
+int leaf_op_classify(const float* feat, const float* class_feat, const int32_t* labels, int B, int rho, int D, int C, float* loss,
+                     int32_t* pred, float* logits, int32_t* best_idx, float* best_feat, leaf_stream_t s);
 int leaf_op_attention_fwd(const void* qkv, void* out, int n_seq, int ctx, int heads, int width, int dtype,
                           leaf_stream_t s);
 int leaf_op_layernorm(const float* x, const float* g, const float* b, float eps, void* out16, int rows, int width,

@@ -5,6 +5,8 @@ Restates the reference's deterministic attacks (utils_attacks.py):
 * ``attack_text_charmer_inference``   utils_attacks.py:451-580 -- the original Charmer attack, the one the reference uses to
   MEASURE robustness (eval_textfare.py:129-130, eval_retrieval.py:78) and to train with under ``--use_charmer`` (utils_AT.py:297-304)
 * ``attack_text_bruteforce``          utils_attacks.py:395-449 -- every position x every character (eval_textfare.py:131-132)
+* ``attack_text_charmer_classification`` utils_attacks.py:582-643 -- Charmer with the margin loss over a class matrix and a stop
+  per caption as soon as its prediction flips: the attack of the zero-shot text classification evaluation (eval_zero_shot_text.py)
 
 Each edit of Charmer has two stages.  Stage 1 scores, for every position z in 0..2L of the expanded view (``generate_sentence``),
 the insert / replace-with / delete-a-space edit and keeps the top-n positions; stage 2 scores every character of V at those positions
@@ -125,6 +127,37 @@ def select_topk(loss, count, n: int, col_offset: int = 0, accumulate: bool = Fal
     return idx, val
 
 
+def margin_scores(feat, class_features, labels, rho: int, want_logits: bool = False, want_features: bool = False):
+    """``leaf_op_classify`` (leaf_amd/csrc/classify.hip) on given unit feature rows ``feat`` fp32 CUDA [B * rho, D]: the score of
+    ``LeafCLIPText.score_candidates_cls`` without the forward.  ``class_features`` fp32 CUDA [C, D] unit rows, ``labels`` [B] host
+    ints, checked here to lie in [0, C).  Returns (best_idx [B], best_feat [B, D] or None, loss [B, rho], pred [B, rho],
+    logits [B * rho, C] or None)."""
+    import torch
+    from . import _lib
+    feat = feat.contiguous()
+    dev = feat.device
+    cf = class_features.to(device=dev, dtype=torch.float32).contiguous()
+    n_cls, D = int(cf.shape[0]), int(feat.shape[1])
+    lab = np.ascontiguousarray(np.asarray(labels).reshape(-1), dtype=np.int64)
+    B = int(lab.size)
+    if feat.shape[0] != B * rho or cf.shape[1] != D:
+        raise ValueError(f"feat {tuple(feat.shape)} / class_features {tuple(cf.shape)} do not match B * rho = {B} * {rho}")
+    if B and (lab.min() < 0 or lab.max() >= n_cls):
+        raise ValueError(f"label outside [0, {n_cls}): {lab[(lab < 0) | (lab >= n_cls)][:4].tolist()}")
+    lab_dev = torch.from_numpy(lab.astype(np.int32)).to(dev)
+    idx = torch.empty(B, dtype=torch.int32, device=dev)
+    best = torch.empty(B, D, dtype=torch.float32, device=dev) if want_features else None
+    loss = torch.empty(B, rho, dtype=torch.float32, device=dev)
+    pred = torch.empty(B, rho, dtype=torch.int32, device=dev)
+    logits = torch.empty(B * rho, n_cls, dtype=torch.float32, device=dev) if want_logits else None
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+    _lib.check(_lib.lib().leaf_op_classify(feat.data_ptr(), cf.data_ptr(), lab_dev.data_ptr(), B, rho, D, n_cls, loss.data_ptr(),
+                                           pred.data_ptr(), logits.data_ptr() if want_logits else None, idx.data_ptr(),
+                                           best.data_ptr() if want_features else None, stream), "leaf_op_classify")
+    return idx, best, loss, pred, logits
+
+
 def new_accumulator(B: int, device):
     """(idx, val) = (-1, -inf) per row: the start of an ``accumulate`` chain"""
     import torch
@@ -138,11 +171,15 @@ class _Scorer:
     Under prefix reuse (EOT trimming on) only the positions from a candidate's first changed token on are computed, from the
     clean captions' K/V (``encode_text_kv``, once per edit); with ``dedupe`` a candidate whose id row repeats an earlier one of the
     same caption (the CLIP tokenizer lower-cases and collapses whitespace: 'a' / 'A', the -1 edit at every even position, a space
-    next to a space) is not computed again: its slot gets the no-op edit and the first occurrence's loss is copied into it."""
+    next to a space) is not computed again: its slot gets the no-op edit and the first occurrence's loss is copied into it.
+    With ``class_features`` (unit rows [C, D]) the score is the classification margin loss (``score_candidates_cls``): ``loss`` then
+    takes the captions' labels (host int array) where it takes their anchors otherwise and returns (loss, pred), duplicates
+    copying both."""
 
-    def __init__(self, model, objective, dedupe, stats):
+    def __init__(self, model, objective, dedupe, stats, class_features=None):
         self.model = model
         self.objective = objective
+        self.class_features = class_features      # classification mode: ``loss`` takes the captions' labels in the anchors' place
         self.reuse = hasattr(model, "encode_text_kv") and getattr(model, "trim_rows", False)
         self.dedupe = dedupe and self.reuse
         self.stats = stats
@@ -150,9 +187,17 @@ class _Scorer:
     def kv(self, base, slot):
         return self.model.encode_text_kv(base, slot=slot) if self.reuse else None
 
+    def _score(self, toks, target_g, R, lens, pl, kv):
+        if self.class_features is None:
+            _, _, loss = self.model.score_candidates(toks, target_g, R, self.objective, want_features=False, want_loss=True,
+                                                     seq_lens=lens, prefix_lens=pl, kv=kv)
+            return loss, None
+        _, _, loss, pred, _ = self.model.score_candidates_cls(toks, self.class_features, target_g, R, seq_lens=lens, prefix_lens=pl, kv=kv)
+        return loss, pred
+
     def loss(self, toks, lens, base, kv, anchor_g, R, count):
         import torch
-        Bg = anchor_g.shape[0]
+        Bg = len(anchor_g)
         pl = None
         if self.reuse:
             neq = toks.reshape(Bg, R, -1) != base[:, None, :]
@@ -178,16 +223,16 @@ class _Scorer:
                 lens[flat] = (base.argmax(-1) + 1)[rep]
             pl = pl.copy()
             pl[flat] = toks.shape[-1]                    # nothing differs from the clean caption: one row under prefix reuse
-            _, _, loss = self.model.score_candidates(toks, anchor_g, R, self.objective, want_features=False, want_loss=True,
-                                                     seq_lens=lens, prefix_lens=pl, kv=kv)
+            loss, pred = self._score(toks, anchor_g, R, lens, pl, kv)
             dup_dev = torch.from_numpy(dup.astype(np.int64)).pin_memory().to(loss.device, non_blocking=True)
             loss = loss.gather(1, dup_dev)
+            if pred is not None:
+                pred = pred.gather(1, dup_dev)
         else:
-            _, _, loss = self.model.score_candidates(toks, anchor_g, R, self.objective, want_features=False, want_loss=True,
-                                                     seq_lens=lens, prefix_lens=pl, kv=kv)
+            loss, pred = self._score(toks, anchor_g, R, lens, pl, kv)
         if self.stats is not None:
             self.stats["computed_rows"] = self.stats.get("computed_rows", 0) + (self.model.rows_scored - rows0)
-        return loss
+        return loss if self.class_features is None else (loss, pred)
 
 
 def _to_host(t):
@@ -333,6 +378,115 @@ def attack_text_charmer(model, tokenizer, sentences, anchor_features, objective:
     return sentences, [max(k, 1)] * B
 
 
+def attack_text_charmer_classification_batched(model, tokenizer, sentences, class_features, labels, n: int = 10, k: int = 1, V=DEFAULT_V,
+                                               dedupe: bool = True, pipeline: Optional[int] = None, max_rows: int = 65536,
+                                               return_trace: Optional[list] = None, return_losses: Optional[list] = None,
+                                               return_picks: Optional[list] = None, return_preds: Optional[list] = None,
+                                               stats: Optional[dict] = None, scorer=None):
+    """Charmer with the classification margin loss (attack_text_charmer_classification, utils_attacks.py:582-643) on a batch of
+    captions.  ``class_features`` fp32 CUDA [C, D], unit rows -- the caller normalises them, nothing is normalised here --,
+    ``labels`` [B] host ints in [0, C).  Each candidate's loss is max_{c != label} logit[c] - logit[label] over its cosine
+    similarities to the classes (margin_loss_lm, :145-151), on the device (leaf_amd/csrc/classify.hip).  Stages, the never-scored
+    last candidate of each stage and the selection are those of ``attack_text_charmer``.
+
+    Early stop (:641): after an edit, caption b stops when the predicted class of its picked candidate differs from labels[b]; it
+    leaves the active set and the later edits run on the remaining captions only.  A caption that is misclassified before the first
+    edit still receives that edit, as in the reference.  Returns (adversarial sentences, dists) with dists[b] the number of edits
+    caption b received (the reference's ``dist + 1``); an empty caption is returned unchanged with dist 0 (the reference raises).
+
+    Stage 1 keeps min(n, count[b]) positions.  The reference's ``min(n, text_sims.shape[0])`` (:611) is the same number whenever the
+    stage fits one of its 2,560-row chunks; for a longer sentence it takes the LAST chunk's row count, which is not reproduced.
+    There is no ``constrain`` argument (the reference's attack has none).  No random numbers are drawn: grouping, pipelining and
+    ``dedupe`` change no sentence, dist or loss bit.
+
+    Hooks as in ``attack_text_charmer`` (two entries per edit; a caption that has stopped has empty entries); ``return_preds``
+    receives per edit the predicted class of each caption's pick (None for a caption that did not take part).  ``scorer``: a test
+    seam, an object with ``reuse`` / ``kv`` / ``loss`` like ``_Scorer`` in classification mode."""
+    import torch
+    sentences = list(sentences)
+    B = len(sentences)
+    labels = np.asarray(labels, dtype=np.int64).reshape(-1)
+    if labels.size != B:
+        raise ValueError(f"{labels.size} labels for {B} sentences")
+    if scorer is None:
+        scorer = _Scorer(model, None, dedupe, stats, class_features=class_features)
+    if pipeline is None:
+        pipeline = 2 if (scorer.reuse and B >= 64) else 1
+    nv = len(V)
+    dists = [0] * B
+    active = [b for b, S in enumerate(sentences) if len(S) > 0]
+    for _ in range(k):
+        if not active:
+            break
+        groups = _groups(active, pipeline, lambda b: max(2 * len(sentences[b]), min(n, 2 * len(sentences[b])) * nv), max_rows)
+        base_all = tokenizer.encode_batch(sentences) if scorer.reuse else None
+        st1 = []
+        for gi, g in enumerate(groups):
+            sg = [sentences[b] for b in g]
+            base = base_all[g] if scorer.reuse else None
+            kv = scorer.kv(base, gi)          # the clean captions once per edit: their K/V serve both stages
+            z, c, count = stage1_plan(sg)
+            R = z.shape[1]
+            if R > SCORE_MAX_COLUMNS:
+                raise ValueError(f"a caption of {max(map(len, sg))} characters: stage 1 has {R} candidates, more than the "
+                                 f"{SCORE_MAX_COLUMNS} per caption one scoring launch takes")
+            toks, lens = prepare_stage(tokenizer, sg, z, c, False)
+            loss, _ = scorer.loss(toks, lens, base, kv, labels[g], R, count)
+            idx, _ = select_topk(loss, count, n)
+            st1.append((sg, base, kv, z, c, count, _to_host(idx), _to_host(loss) if return_losses is not None else None))
+        st2 = []
+        for g, (sg, base, kv, z1, c1, count1, fin, fin_loss) in zip(groups, st1):
+            top = fin()
+            m = np.minimum(n, count1)
+            st1_out = (render_plan(sg, z1, c1, count1) if return_trace is not None else None,
+                       [fin_loss()[i, :count1[i]] for i in range(len(sg))] if fin_loss is not None else None,
+                       [top[i, :m[i]] for i in range(len(sg))])
+            z, c, count = stage2_plan(top, m, V)
+            R = z.shape[1]
+            if R > SCORE_MAX_COLUMNS:
+                raise ValueError(f"stage 2 has {R} = n |V| candidates per caption, more than the {SCORE_MAX_COLUMNS} one scoring "
+                                 f"launch takes: lower n")
+            toks, lens = prepare_stage(tokenizer, sg, z, c, False)
+            loss, pred = scorer.loss(toks, lens, base, kv, labels[g], R, count)
+            idx, _ = select_topk(loss, count, 1)
+            pick_pred = pred.gather(1, idx.clamp(min=0).long())          # the predicted class of the pick (a row without one: unused)
+            st2.append((sg, z, c, count, _to_host(idx), _to_host(pick_pred), _to_host(loss) if return_losses is not None else None,
+                        st1_out))
+        trace1, trace2 = ([[] for _ in range(B)] for _ in range(2))
+        loss1, loss2 = ([np.zeros(0, np.float32) for _ in range(B)] for _ in range(2))
+        pick1, pick2 = ([np.zeros(0, np.int64) for _ in range(B)] for _ in range(2))
+        preds = [None] * B
+        still = []
+        for g, (sg, z, c, count, fin, fin_pred, fin_loss, st1_out) in zip(groups, st2):
+            best, bpred = fin()[:, 0], fin_pred()[:, 0]
+            lh = fin_loss() if fin_loss is not None else None
+            strings = render_plan(sg, z, c, count) if return_trace is not None else None
+            for i, b in enumerate(g):
+                j = int(best[i])
+                if j >= 0:
+                    sentences[b] = _apply_edit(sg[i], int(z[i, j]), int(c[i, j]))
+                    dists[b] += 1
+                    preds[b] = int(bpred[i])
+                    if preds[b] == labels[b]:
+                        still.append(b)               # still classified as its label: it takes the next edit
+                if st1_out[0] is not None:
+                    trace1[b], trace2[b] = st1_out[0][i], strings[i]
+                if st1_out[1] is not None:
+                    loss1[b], loss2[b] = st1_out[1][i], lh[i, :count[i]]
+                pick1[b] = st1_out[2][i]
+                pick2[b] = np.array([j] if j >= 0 else [], dtype=np.int64)
+        if return_trace is not None:
+            return_trace += [trace1, trace2]
+        if return_losses is not None:
+            return_losses += [loss1, loss2]
+        if return_picks is not None:
+            return_picks += [pick1, pick2]
+        if return_preds is not None:
+            return_preds.append(preds)
+        active = still
+    return sentences, dists
+
+
 def attack_text_bruteforce_batched(model, tokenizer, sentences, anchor_features, objective: str = "l2", V=DEFAULT_V,
                                    constrain: bool = False, debug: bool = False, dedupe: bool = True, chunk_cols: int = 4096,
                                    max_rows: int = 65536, return_losses: Optional[list] = None, stats: Optional[dict] = None):
@@ -424,3 +578,16 @@ def attack_text_bruteforce(model, tokenizer, sentence, anchor_features, device=N
     ``batch_size`` changes nothing."""
     adv, dists = attack_text_bruteforce_batched(model, tokenizer, [sentence], _one(anchor_features), objective, V, constrain, debug)
     return adv[0], dists[0]
+
+
+def attack_text_charmer_classification(model, tokenizer, sentence, image_features, label, device=None, n=10, k=1, V=DEFAULT_V, debug=False,
+                                       batch_size=128 * 20):
+    """utils_attacks.py:582-643 with its signature and return (sentence, dist).  ``image_features`` [C, D]: the class matrix, unit
+    rows (the reference does not normalise it either).  ``batch_size`` is accepted for compatibility and changes nothing.  An empty
+    sentence is returned unchanged with dist 0 (the reference raises)."""
+    adv, dists = attack_text_charmer_classification_batched(model, tokenizer, [sentence], image_features.reshape(len(image_features), -1),
+                                                            [int(label)], n, k, V)
+    if debug:
+        print(adv[0])
+    return adv[0], dists[0]
+

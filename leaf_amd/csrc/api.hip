@@ -376,18 +376,58 @@ int score_check(bool extra_ok, leaf_text_t h, const float* params, const void* w
     if (objective < 0 || objective > 3) { leaf_set_error("unknown objective %d", objective); return 1; }
     return 0;
 }
+// what a scoring pass compares its candidates with: one anchor row per caption under one of the four objectives (leaf_launch_score),
+// or a class matrix shared by all captions with a label per caption (leaf_launch_classify, classify.hip)
+struct ScoreTarget {
+    const float* anchor = nullptr;       // [B, D]
+    int objective = 0;
+    const float* class_feat = nullptr;   // [C, D], unit rows; non-null selects the classification margin loss
+    int C = 0;
+    const int32_t* labels = nullptr;     // [B], device
+    int32_t* pred = nullptr;             // [B, rho] or null
+    float* logits = nullptr;             // [B * rho, C] or null
+};
+ScoreTarget anchor_target(const float* anchor, int objective) {
+    ScoreTarget t;
+    t.anchor = anchor;
+    t.objective = objective;
+    return t;
+}
+// argument checks of the two classification entries on top of score_check's (loss is required: best_idx is taken from it)
+int cls_check(const float* class_feat, int C, const int32_t* labels, const float* loss, int rho) {
+    if (!class_feat || !labels || !loss) { leaf_set_error("null/invalid argument"); return 1; }
+    if (C < LEAF_CLS_MIN_CLASSES || C > LEAF_CLS_MAX_CLASSES) {
+        leaf_set_error("%d classes: the classification score takes %d .. %d", C, LEAF_CLS_MIN_CLASSES, LEAF_CLS_MAX_CLASSES);
+        return 1;
+    }
+    if (rho > LEAF_SCORE_MAX_RHO) { leaf_set_error("rho %d: one scoring launch takes %d candidates per caption", rho, LEAF_SCORE_MAX_RHO); return 1; }
+    return 0;
+}
+ScoreTarget class_target(const float* class_feat, int C, const int32_t* labels, int32_t* pred, float* logits) {
+    ScoreTarget t;
+    t.class_feat = class_feat;
+    t.C = C;
+    t.labels = labels;
+    t.pred = pred;
+    t.logits = logits;
+    return t;
+}
 // features of the pass's n_seq sequences -> workspace, then the best of the rho candidates of each of the B captions: the candidates
 // are the LAST B * rho sequences of the pass (the fused first stage has its B captions in front of them)
 int score_pass(leaf_text_t h, const float* params, const void* w16_fwd, const int32_t* tokens, const int32_t* lens, const int32_t* cu,
-               int n_seq, const PrefixPlan& pp, const float* anchor, int B, int rho, int objective, int32_t* best_idx, float* best_feat,
+               int n_seq, const PrefixPlan& pp, const ScoreTarget& tg, int B, int rho, int32_t* best_idx, float* best_feat,
                float* loss, void* ws, size_t ws_bytes, hipStream_t s) {
     const int D = h->cfg.embed_dim;
     Carver c(ws, ws_bytes);
     float* feat = (float*)c.take((size_t)n_seq * D * 4);
-    const int normalize = (objective == LEAF_OBJ_SIM || objective == LEAF_OBJ_DISSIM);
+    const int normalize = (tg.class_feat || tg.objective == LEAF_OBJ_SIM || tg.objective == LEAF_OBJ_DISSIM);
     const int rc = forward_all(h, params, w16_fwd, tokens, lens, cu, n_seq, feat, normalize, c, s, pp);
     if (rc) return rc;
-    LEAF_TRY(leaf_launch_score(feat + (size_t)(n_seq - B * rho) * D, anchor, B, rho, D, objective, best_idx, best_feat, loss, s));
+    const float* cand = feat + (size_t)(n_seq - B * rho) * D;
+    if (tg.class_feat)
+        LEAF_TRY(leaf_launch_classify(cand, tg.class_feat, tg.labels, B, rho, D, tg.C, loss, tg.pred, tg.logits, best_idx, best_feat, s));
+    else
+        LEAF_TRY(leaf_launch_score(cand, tg.anchor, B, rho, D, tg.objective, best_idx, best_feat, loss, s));
     return 0;
 }
 }  // namespace
@@ -397,8 +437,18 @@ extern "C" int leaf_score_candidates(leaf_text_t h, const float* params, const v
                                      int rho, int objective, int32_t* best_idx,
                                      float* best_feat, float* loss, void* ws, size_t ws_bytes, leaf_stream_t s) {
     if (score_check(true, h, params, w16_fwd, tokens, anchor, best_idx, ws, B, rho, objective)) return 1;
-    return score_pass(h, params, w16_fwd, tokens, seq_lens, cu_rows, B * rho, PrefixPlan(), anchor, B, rho, objective, best_idx, best_feat,
+    return score_pass(h, params, w16_fwd, tokens, seq_lens, cu_rows, B * rho, PrefixPlan(), anchor_target(anchor, objective), B, rho, best_idx, best_feat,
                       loss, ws, ws_bytes, (hipStream_t)s);
+}
+
+// the same pass scored against a class matrix (classify.hip); score_check's anchor slot carries the class matrix, objective 0 is unused
+extern "C" int leaf_score_candidates_cls(leaf_text_t h, const float* params, const void* w16_fwd, const int32_t* tokens,
+                                         const int32_t* seq_lens, const int32_t* cu_rows, const float* class_feat, int C,
+                                         const int32_t* labels, int B, int rho, int32_t* best_idx, float* best_feat, float* loss,
+                                         int32_t* pred, float* logits, void* ws, size_t ws_bytes, leaf_stream_t s) {
+    if (score_check(true, h, params, w16_fwd, tokens, class_feat, best_idx, ws, B, rho, 0) || cls_check(class_feat, C, labels, loss, rho)) return 1;
+    return score_pass(h, params, w16_fwd, tokens, seq_lens, cu_rows, B * rho, PrefixPlan(), class_target(class_feat, C, labels, pred, logits),
+                      B, rho, best_idx, best_feat, loss, ws, ws_bytes, (hipStream_t)s);
 }
 
 // ------------------------------------------------------------------ prefix reuse
@@ -434,13 +484,9 @@ extern "C" int leaf_text_forward_kv(leaf_text_t h, const float* params, const vo
                          (hipStream_t)s, kvp, max_len);
 }
 
-extern "C" int leaf_score_candidates_prefix(leaf_text_t h, const float* params, const void* w16_fwd, const int32_t* tokens,
-                                            const int32_t* suffix_lens, const int32_t* cu_suffix, const int32_t* prefix,
-                                            const int32_t* base_cu, const void* kv, size_t base_rows, int max_len,
-                                            const float* anchor, int B, int rho, int objective, int32_t* best_idx, float* best_feat, float* loss,
-                                            void* ws, size_t ws_bytes, leaf_stream_t s) {
-    if (score_check(suffix_lens && cu_suffix && prefix && base_cu && kv, h, params, w16_fwd, tokens, anchor, best_idx, ws, B, rho, objective))
-        return 1;
+// the prefix map of a leaf_score_candidates_prefix* pass: candidates grouped rho per caption, earlier positions read from `kv`
+static PrefixPlan prefix_plan(leaf_text_t h, const int32_t* prefix, const int32_t* base_cu, const void* kv, size_t base_rows, int max_len,
+                              int rho) {
     PrefixPlan pp;
     pp.prefix_dev = prefix;
     pp.base_cu_dev = base_cu;
@@ -448,8 +494,30 @@ extern "C" int leaf_score_candidates_prefix(leaf_text_t h, const float* params, 
     pp.kv = (const uint16_t*)kv;
     pp.kv_stride = base_rows * 3 * h->cfg.width;
     pp.group = rho;
-    return score_pass(h, params, w16_fwd, tokens, suffix_lens, cu_suffix, B * rho, pp, anchor, B, rho, objective, best_idx, best_feat, loss,
+    return pp;
+}
+extern "C" int leaf_score_candidates_prefix(leaf_text_t h, const float* params, const void* w16_fwd, const int32_t* tokens,
+                                            const int32_t* suffix_lens, const int32_t* cu_suffix, const int32_t* prefix,
+                                            const int32_t* base_cu, const void* kv, size_t base_rows, int max_len,
+                                            const float* anchor, int B, int rho, int objective, int32_t* best_idx, float* best_feat, float* loss,
+                                            void* ws, size_t ws_bytes, leaf_stream_t s) {
+    if (score_check(suffix_lens && cu_suffix && prefix && base_cu && kv, h, params, w16_fwd, tokens, anchor, best_idx, ws, B, rho, objective))
+        return 1;
+    return score_pass(h, params, w16_fwd, tokens, suffix_lens, cu_suffix, B * rho, prefix_plan(h, prefix, base_cu, kv, base_rows, max_len, rho), anchor_target(anchor, objective), B, rho, best_idx, best_feat, loss,
                       ws, ws_bytes, (hipStream_t)s);
+}
+
+extern "C" int leaf_score_candidates_prefix_cls(leaf_text_t h, const float* params, const void* w16_fwd, const int32_t* tokens,
+                                                const int32_t* suffix_lens, const int32_t* cu_suffix, const int32_t* prefix,
+                                                const int32_t* base_cu, const void* kv, size_t base_rows, int max_len,
+                                                const float* class_feat, int C, const int32_t* labels, int B, int rho,
+                                                int32_t* best_idx, float* best_feat, float* loss, int32_t* pred, float* logits,
+                                                void* ws, size_t ws_bytes, leaf_stream_t s) {
+    if (score_check(suffix_lens && cu_suffix && prefix && base_cu && kv, h, params, w16_fwd, tokens, class_feat, best_idx, ws, B, rho, 0) ||
+        cls_check(class_feat, C, labels, loss, rho))
+        return 1;
+    return score_pass(h, params, w16_fwd, tokens, suffix_lens, cu_suffix, B * rho, prefix_plan(h, prefix, base_cu, kv, base_rows, max_len, rho),
+                      class_target(class_feat, C, labels, pred, logits), B, rho, best_idx, best_feat, loss, ws, ws_bytes, (hipStream_t)s);
 }
 
 // The clean-caption K/V pass and the FIRST stage's scoring in one pass: sequences 0 .. B-1 are the captions (full rows, prefix 0),
@@ -474,7 +542,7 @@ extern "C" int leaf_score_candidates_prefix_fused(leaf_text_t h, const float* pa
     pp.group_off = B;
     pp.kv_copy = (uint16_t*)kv;
     pp.kv_self_rows = base_rows;
-    return score_pass(h, params, w16_fwd, tokens, seq_lens, cu_rows, B + B * rho, pp, anchor, B, rho, objective, best_idx, best_feat, loss,
+    return score_pass(h, params, w16_fwd, tokens, seq_lens, cu_rows, B + B * rho, pp, anchor_target(anchor, objective), B, rho, best_idx, best_feat, loss,
                       ws, ws_bytes, (hipStream_t)s);
 }
 
@@ -599,6 +667,14 @@ extern "C" int leaf_op_layernorm_bwd(const float* dy, const float* x, const floa
     ra.part = (const float*)ws; ra.n = 1; ra.grid = leaf_ln_bwd_grid(rows, d); ra.d = d; ra.inv_s = gscale + 1;
     ra.dg[0] = dg; ra.db[0] = db;
     return leaf_check(leaf_launch_ln_param_reduce(ra, (hipStream_t)s), "ln_param_reduce");
+}
+// the classification score alone (classify.hip) on given feature rows: the kernel hook of tests/test_gpu_zeroshot.py
+extern "C" int leaf_op_classify(const float* feat, const float* class_feat, const int32_t* labels, int B, int rho, int D, int C, float* loss,
+                                int32_t* pred, float* logits, int32_t* best_idx, float* best_feat, leaf_stream_t s) {
+    if (!feat || !best_idx || B < 1 || rho < 1 || D < 1) { leaf_set_error("null/invalid argument"); return 1; }
+    if (cls_check(class_feat, C, labels, loss, rho)) return 1;
+    return leaf_check(leaf_launch_classify(feat, class_feat, labels, B, rho, D, C, loss, pred, logits, best_idx, best_feat, (hipStream_t)s),
+                      "classify");
 }
 extern "C" int leaf_op_project_rows(const float* xg, const float* g, const float* b, float eps, const float* proj,
                                     float* xn_scratch, float* out, int M, int d, int D, int normalize, leaf_stream_t s) {

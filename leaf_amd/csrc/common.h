@@ -144,6 +144,20 @@ __device__ __forceinline__ float wave_max(float v) {
     return v;
 }
 
+// the total order of every selection here (select.hip, classify.hip):
+// (v, j) ranks before (w, k): NaN above every number (torch.topk / argmax), then the larger value, then the lower column
+__device__ __forceinline__ bool ranks_before(float v, int j, float w, int k) {
+    const bool nv = __builtin_isnan(v), nw = __builtin_isnan(w);
+    if (nv != nw) return nv;
+    if (!nv && v != w) return v > w;
+    return j < k;
+}
+
+// j < 0 marks "nothing yet"
+__device__ __forceinline__ void keep_better(float& bv, int& bj, float v, int j) {
+    if (j >= 0 && (bj < 0 || ranks_before(v, j, bv, bj))) { bv = v; bj = j; }
+}
+
 // x + (x of another lane of the same 16-lane row), as ONE VALU instruction (v_add_f32 with a DPP source): quad_perm
 // [1,0,3,2] / [2,3,0,1] exchange inside a quad, row_half_mirror reverses each 8-lane half, row_mirror the 16-lane row.
 // Applied in that order to a value they form an all-reduce over 16 lanes whose pairing is the xor-butterfly 1, 2, 4, 8

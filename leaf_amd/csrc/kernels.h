@@ -129,6 +129,12 @@ hipError_t leaf_launch_pool_project(const float* x, const int32_t* tokens, const
 // loss[b,r] per objective, arg-max over rho (first maximum wins), best feature gather
 hipError_t leaf_launch_score(const float* feat, const float* anchor, int B, int rho, int D, int objective,
                              int32_t* best_idx, float* best_feat, float* loss, hipStream_t s);
+// classify.hip: margin loss of feat [B*rho, D] (unit rows) over the class matrix class_feat [C, D] with label [B] (device):
+// loss [B, rho] (required), pred [B*rho], logits [B*rho, C], best_feat [B, D] (each may be null), best_idx [B] = first of the loss row
+// in the order of leaf_select_topk.  LEAF_CLS_MIN_CLASSES <= C <= LEAF_CLS_MAX_CLASSES and rho <= LEAF_SCORE_MAX_RHO, else an error.
+constexpr int LEAF_SCORE_MAX_RHO = 8192;        // candidates per caption of one scoring launch (leaf_launch_score, leaf_launch_classify)
+hipError_t leaf_launch_classify(const float* feat, const float* class_feat, const int32_t* label, int B, int rho, int D, int C,
+                                float* loss, int32_t* pred, float* logits, int32_t* best_idx, float* best_feat, hipStream_t s);
 // device-to-device byte copy in one launch
 hipError_t leaf_launch_copy_bytes(const void* src, void* dst, size_t bytes, hipStream_t s);
 hipError_t leaf_launch_iota(int32_t* out, int n, hipStream_t s);      // out[i] = i

@@ -14,19 +14,6 @@
 
 namespace {
 
-// (v, j) ranks before (w, k): NaN above every number (torch.topk / argmax), then the larger value, then the lower column
-__device__ __forceinline__ bool ranks_before(float v, int j, float w, int k) {
-    const bool nv = __builtin_isnan(v), nw = __builtin_isnan(w);
-    if (nv != nw) return nv;
-    if (!nv && v != w) return v > w;
-    return j < k;
-}
-
-// j < 0 marks "nothing yet"
-__device__ __forceinline__ void keep_better(float& bv, int& bj, float v, int j) {
-    if (j >= 0 && (bj < 0 || ranks_before(v, j, bv, bj))) { bv = v; bj = j; }
-}
-
 __global__ __launch_bounds__(256) void select_topk_kernel(const float* __restrict__ loss, int ld, const int32_t* __restrict__ count,
                                                           int n, int col_offset, int accumulate, int32_t* __restrict__ idx,
                                                           float* __restrict__ val) {

@@ -499,12 +499,12 @@ class LeafCLIPText:
             self.score_candidates_prepare(tokens, anchor, rho, objective, want_features, want_loss, seq_lens, kv, single_edit), prefix_lens)
 
     def score_candidates_prepare(self, tokens, anchor, rho, objective="l2", want_features=True, want_loss=False, seq_lens=None, kv=None,
-                                 single_edit: bool = False):
+                                 single_edit: bool = False, cls=None):
         """Everything of a prefix-reuse ``score_candidates`` call that does NOT depend on the prefix lengths: token / anchor placement,
         output buffers, the length limits and a pinned staging buffer for the row plan.  The search calls this BEFORE it waits for the
         previous stage's winners and ``score_candidates_run(plan, prefix_lens)`` right after them: the device idles at that boundary
         for as long as the host needs between the two (round 4, tools/stage_hole_probe.py: 270 -> 94 us at ViT-L B = 128, 181 -> 123 us at ViT-H
-        B = 32)."""
+        B = 32).  ``cls`` (from ``_cls_target``; ``anchor`` is then None): score against a class matrix, ``score_candidates_cls``."""
         if not self._packed:
             self.pack()
         if seq_lens is None:
@@ -518,7 +518,7 @@ class LeafCLIPText:
         if isinstance(tokens, np.ndarray):
             tokens = torch.from_numpy(tokens)
         t = self._tokens(tokens.reshape(-1, tokens.shape[-1]))
-        B = anchor.shape[0]
+        B = anchor.shape[0] if cls is None else cls["B"]
         if t.shape[0] != B * rho or kv["n"] != B or n != B * rho:
             raise ValueError("candidate rows / kv cache do not match B*rho")
         if kv.get("arith", self.arithmetic_tag()) != self.arithmetic_tag():
@@ -531,13 +531,14 @@ class LeafCLIPText:
                                  "that did not run with single_edit): rebuild it with encode_text_kv or score_candidates_fused(single_edit=True)")
             if not np.array_equal(full, np.repeat(kv["lens"].astype(np.int32), rho)):
                 raise ValueError("single_edit pass: a candidate's length differs from its caption's")
-        anchor = anchor.to(device=self.device, dtype=torch.float32).contiguous()
+        if cls is None:
+            anchor = anchor.to(device=self.device, dtype=torch.float32).contiguous()
         idx = torch.empty(B, dtype=torch.int32, device=self.device)
         feat = torch.empty(B, self.cfg.embed_dim, dtype=torch.float32, device=self.device) if want_features else None
-        loss = torch.empty(B, rho, dtype=torch.float32, device=self.device) if want_loss else None
+        loss = torch.empty(B, rho, dtype=torch.float32, device=self.device) if (want_loss or cls is not None) else None
         return {"full": full, "limit": limit, "host": host, "t": t, "anchor": anchor, "idx": idx, "feat": feat, "loss": loss, "B": B,
                 "rho": rho, "obj": _OBJ[objective], "kv": kv, "ws": self._workspace(1, B * rho), "max_len": int(full.max()),
-                "want_loss": want_loss, "single_edit": bool(single_edit)}
+                "want_loss": want_loss, "single_edit": bool(single_edit), "cls": cls}
 
     def score_candidates_run(self, plan, prefix_lens):
         """The prefix-dependent rest of ``score_candidates_prepare``: row plan (suffix rows per candidate, their running sum), one
@@ -552,6 +553,15 @@ class LeafCLIPText:
         dev = plan["host"].to(self.device, non_blocking=True)
         cu_dev, pfx_dev = dev[:n + 1], dev[n + 1:]
         self.rows_scored += int(hv[n])
+        cls = plan.get("cls")
+        if cls is not None:
+            pred, logits = self._cls_outputs(cls, plan["B"], plan["rho"])
+            _lib.check(self._lib.leaf_score_candidates_prefix_cls(
+                self._h, _ptr(self.flat), _ptr(self.w16), _ptr(plan["t"]), C.c_void_p(suf.ctypes.data), _ptr(cu_dev), _ptr(pfx_dev),
+                _ptr(kv["base_cu"]), _ptr(kv["kv"]), kv["base_rows"], plan["max_len"], _ptr(cls["class_feat"]), cls["C"], _ptr(cls["labels"]),
+                plan["B"], plan["rho"], _ptr(plan["idx"]), _ptr(plan["feat"]), _ptr(plan["loss"]), _ptr(pred), _ptr(logits),
+                _ptr(plan["ws"]), plan["ws"].numel(), self._stream()), "leaf_score_candidates_prefix_cls")
+            return plan["idx"], plan["feat"], (plan["loss"] if plan["want_loss"] else None), pred, logits
         single_edit = plan.get("single_edit", False)
         if single_edit and os.environ.get("LEAF_VERIFY_SINGLE_EDIT") == "1":
             if kv.get("tokens") is None:
@@ -563,6 +573,59 @@ class LeafCLIPText:
             _ptr(plan["idx"]), _ptr(plan["feat"]), _ptr(plan["loss"]), _ptr(plan["ws"]), plan["ws"].numel(), self._stream()),
             "leaf_score_candidates_prefix"))
         return (plan["idx"], plan["feat"], plan["loss"]) if plan["want_loss"] else (plan["idx"], plan["feat"])
+
+    # ------------------------------------------------------------------ classification scoring (classify.hip)
+    def _cls_target(self, class_features, labels, want_pred, want_logits):
+        """the class matrix and labels of a ``score_candidates_cls`` call on the device, checked on the host: embed_dim columns, every
+        label in [0, C) (the kernel cannot report a bad label; the engine itself refuses a class count outside 2 .. 1,024)"""
+        cf = class_features.to(device=self.device, dtype=torch.float32).contiguous()
+        if cf.dim() != 2 or cf.shape[1] != self.cfg.embed_dim:
+            raise ValueError(f"class_features must be [C, {self.cfg.embed_dim}], got {tuple(cf.shape)}")
+        n_cls = int(cf.shape[0])
+        lab = labels.cpu().numpy() if isinstance(labels, torch.Tensor) else np.asarray(labels)
+        lab = np.ascontiguousarray(lab.reshape(-1), dtype=np.int64)
+        if lab.size and (lab.min() < 0 or lab.max() >= n_cls):
+            raise ValueError(f"label outside [0, {n_cls}): {lab[(lab < 0) | (lab >= n_cls)][:4].tolist()}")
+        lab_dev = torch.from_numpy(lab.astype(np.int32)).pin_memory().to(self.device, non_blocking=True)
+        return {"class_feat": cf, "C": n_cls, "labels": lab_dev, "B": int(lab.size), "want_pred": want_pred, "want_logits": want_logits}
+
+    def _cls_outputs(self, cls, B, rho):
+        pred = torch.empty(B, rho, dtype=torch.int32, device=self.device) if cls["want_pred"] else None
+        logits = torch.empty(B * rho, cls["C"], dtype=torch.float32, device=self.device) if cls["want_logits"] else None
+        return pred, logits
+
+    def score_candidates_cls(self, tokens, class_features: torch.Tensor, labels, rho: int, want_features=False, want_loss=True,
+                             want_pred=True, want_logits=False, seq_lens=None, prefix_lens=None, kv=None):
+        """The pass of ``score_candidates`` scored against a class matrix shared by all captions (leaf_score_candidates_cls,
+        leaf_amd/csrc/classify.hip; the objective of the reference's attack_text_charmer_classification): the candidates' features are
+        L2-normalised, ``class_features`` [C, D] are unit rows (the caller normalises), ``labels`` [B] (host array or tensor) the true
+        classes.  loss[b, r] = max_{c != labels[b]} logit[c] - logit[labels[b]], pred[b, r] = first arg-max of the logits.
+        Returns (best_idx int32 [B], best_feat [B, D] or None, loss [B, rho] or None, pred int32 [B, rho] or None,
+        logits [B * rho, C] or None).  ``prefix_lens`` / ``kv``: prefix reuse as in ``score_candidates``; same bits."""
+        cls = self._cls_target(class_features, labels, want_pred, want_logits)
+        if prefix_lens is not None and kv is not None and self.trim_rows:
+            return self.score_candidates_run(
+                self.score_candidates_prepare(tokens, None, rho, "l2", want_features, want_loss, seq_lens, kv, cls=cls), prefix_lens)
+        if not self._packed:
+            self.pack()
+        lens_p, cu, keep = self._row_plan(tokens, seq_lens)
+        if isinstance(tokens, np.ndarray):
+            tokens = torch.from_numpy(tokens)
+        t = self._tokens(tokens.reshape(-1, tokens.shape[-1]))
+        B = cls["B"]
+        if t.shape[0] != B * rho:
+            raise ValueError(f"{t.shape[0]} candidate rows != B*rho = {B}*{rho}")
+        idx = torch.empty(B, dtype=torch.int32, device=self.device)
+        feat = torch.empty(B, self.cfg.embed_dim, dtype=torch.float32, device=self.device) if want_features else None
+        loss = torch.empty(B, rho, dtype=torch.float32, device=self.device)
+        pred, logits = self._cls_outputs(cls, B, rho)
+        ws = self._workspace(1, B * rho)
+        self.rows_scored += int(keep.sum()) if keep is not None else B * rho * self.cfg.context_length
+        _lib.check(self._lib.leaf_score_candidates_cls(self._h, _ptr(self.flat), _ptr(self.w16), _ptr(t), lens_p, _ptr(cu),
+                                                       _ptr(cls["class_feat"]), cls["C"], _ptr(cls["labels"]), B, rho, _ptr(idx),
+                                                       _ptr(feat), _ptr(loss), _ptr(pred), _ptr(logits), _ptr(ws), ws.numel(),
+                                                       self._stream()), "leaf_score_candidates_cls")
+        return idx, feat, (loss if want_loss else None), pred, logits
 
     def score_candidates_fused(self, base_tokens, base_lens, tokens, anchor: torch.Tensor, rho: int, seq_lens, prefix_lens,
                                objective: str = "l2", want_features: bool = False, want_loss: bool = False, single_edit: bool = False):
