@@ -24,8 +24,6 @@ import numpy as np
 
 DEFAULT_V = [-1] + [ord(c) for c in string.ascii_lowercase + ' ' + string.ascii_uppercase + string.digits + string.punctuation]
 
-_OBJ = {"l2": 0, "negl2": 1, "dissim": 2, "sim": 3}
-
 
 # ----------------------------------------------------------------------------- string mutation
 def generate_sentence(S: str, z, u, V: Sequence[int], k: int = 1, alternative: Optional[int] = None) -> str:
@@ -363,6 +361,33 @@ def duplicate_map(toks: np.ndarray, B: int, n: int) -> np.ndarray:
     return dup.astype(np.int64)
 
 
+def first_difference(toks: np.ndarray, base: np.ndarray, rho: int) -> np.ndarray:
+    """prefix lengths [B * rho] for prefix reuse: the leading positions where a candidate's ids equal its clean caption's (>= 1:
+    SOT; the context length when nothing differs)"""
+    neq = toks.reshape(len(base), rho, -1) != base[:, None, :]
+    first = neq.argmax(-1)
+    first[~neq.any(-1)] = toks.shape[-1]
+    return first.reshape(-1)
+
+
+def lend_duplicates(toks, lens, pl, base, dup):
+    """Copies of (toks [B * rho, ctx], lens, pl) in which every slot that ``dup`` (``duplicate_map``) marks as a repeat of an earlier
+    candidate is handed to the no-op edit -- the clean caption: ONE recomputed row under prefix reuse.  The caller scores these and
+    copies each first occurrence's loss into its repeats' slots (``loss.gather(1, dup)``): the completed [B, rho] losses are the
+    reference's full loss matrix, and a first-index arg-max over them is its ``torch.argmax`` (utils_attacks.py:348,386)."""
+    B, rho = dup.shape
+    lent = (dup != np.arange(rho)[None, :]).reshape(-1)
+    toks = toks.copy().reshape(B * rho, -1)
+    rep = np.repeat(np.arange(B), rho)[lent]
+    toks[lent] = base[rep]
+    if lens is not None:
+        lens = lens.copy()
+        lens[lent] = (base.argmax(-1) + 1)[rep]
+    pl = pl.copy()
+    pl[lent] = toks.shape[-1]                                # nothing differs from the clean caption
+    return toks, lens, pl
+
+
 def attack_text_leaf(model, tokenizer, sentences, anchor_features, device=None, objective="l2", n=10, k=1,
                      V=DEFAULT_V, constrain=False, debug=False, return_trace: Optional[list] = None,
                      return_picks: Optional[list] = None, dedupe: bool = True, pipeline: Optional[int] = None,
@@ -405,24 +430,15 @@ def attack_text_leaf(model, tokenizer, sentences, anchor_features, device=None, 
     groups = [np.arange(bounds[g], bounds[g + 1]) for g in range(pipeline)]
     dev = anchor_features.device
 
-    def prefix_lens(toks, base, Bg):
-        """leading positions where a candidate's ids equal its clean caption's (>= 1: SOT)"""
-        neq = toks.reshape(Bg, n, -1) != base[:, None, :]
-        first = neq.argmax(-1)
-        first[~neq.any(-1)] = toks.shape[-1]
-        return first.reshape(-1)
-
     def launch(toks, lens, base, kv, anchor_g, want_features):
         """Queue one stage's scoring of one group; returns finish() -> (winner indices [Bg] on the host, winner features or None).
         The indices travel to pinned host memory right behind the scoring launches and finish() waits for THAT copy's event
         only, so work queued later (the next group's scoring) does not delay it.  With ``dedupe`` a candidate whose id row
-        repeats an earlier candidate's of the same caption is not computed again: its slot is handed to the no-op edit (the
-        clean caption: ONE row under prefix reuse), the loss of its first occurrence is copied into it and the arg-max runs over
-        the completed [Bg, rho] losses -- first index wins, so the first occurrence beats its copies exactly as in torch.argmax
-        over the reference's full loss matrix (utils_attacks.py:348,386)."""
+        repeats an earlier candidate's of the same caption is not computed again (``lend_duplicates``): the arg-max runs over
+        the completed [Bg, rho] losses -- first index wins, so the first occurrence beats its copies."""
         wait_anchor()
         Bg = anchor_g.shape[0]
-        pl = prefix_lens(toks, base, Bg) if reuse else None
+        pl = first_difference(toks, base, n) if reuse else None
         dup = duplicate_map(toks, Bg, n) if dedupe else None
         has_dup = dup is not None and bool((dup != np.arange(n)[None, :]).any())
         if not has_dup:
@@ -430,15 +446,7 @@ def attack_text_leaf(model, tokenizer, sentences, anchor_features, device=None, 
                                                prefix_lens=pl, kv=kv)
             both = ids.to(torch.int64)[None, :]
         else:
-            is_dup = (dup != np.arange(n)[None, :]).reshape(-1)
-            toks = toks.copy().reshape(Bg * n, -1)
-            rep = np.repeat(np.arange(Bg), n)[is_dup]
-            toks[is_dup] = base[rep]
-            if lens is not None:
-                lens = lens.copy()
-                lens[is_dup] = (base.argmax(-1) + 1)[rep]
-            pl = pl.copy()
-            pl[is_dup] = toks.shape[-1]                          # nothing differs from the clean caption
+            toks, lens, pl = lend_duplicates(toks, lens, pl, base, dup)
             dup_dev = torch.from_numpy(dup).pin_memory().to(dev, non_blocking=True)
             ids_k, feat, loss = model.score_candidates(toks, anchor_g, n, objective, want_features=want_features, want_loss=True,
                                                        seq_lens=lens, prefix_lens=pl, kv=kv)

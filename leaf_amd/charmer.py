@@ -28,7 +28,7 @@ from typing import List, Optional, Sequence
 
 import numpy as np
 
-from .attacks import DEFAULT_V, _apply_edit, _stage_candidates, duplicate_map
+from .attacks import DEFAULT_V, _apply_edit, _stage_candidates, duplicate_map, first_difference, lend_duplicates
 
 SCORE_MAX_COLUMNS = 8192        # candidates per caption and launch the score kernel takes (elementwise.hip: leaf_launch_score)
 
@@ -167,43 +167,33 @@ def new_accumulator(B: int, device):
 
 # ----------------------------------------------------------------------------- scoring of one padded stage
 class _Scorer:
-    """Scores a padded [Bg, R] plan against the anchors of its captions and returns the COMPLETE loss matrix on the device.
-    Under prefix reuse (EOT trimming on) only the positions from a candidate's first changed token on are computed, from the
-    clean captions' K/V (``encode_text_kv``, once per edit); with ``dedupe`` a candidate whose id row repeats an earlier one of the
-    same caption (the CLIP tokenizer lower-cases and collapses whitespace: 'a' / 'A', the -1 edit at every even position, a space
-    next to a space) is not computed again: its slot gets the no-op edit and the first occurrence's loss is copied into it.
-    With ``class_features`` (unit rows [C, D]) the score is the classification margin loss (``score_candidates_cls``): ``loss`` then
-    takes the captions' labels (host int array) where it takes their anchors otherwise and returns (loss, pred), duplicates
-    copying both."""
+    """Scores a padded [Bg, R] plan against the targets of its captions and returns (the COMPLETE loss matrix on the device, the
+    predicted classes or None).  Under prefix reuse (EOT trimming on) only the positions from a candidate's first changed token on
+    are computed, from the clean captions' K/V (``encode_text_kv``, once per edit); with ``dedupe`` a candidate whose id row repeats
+    an earlier one of the same caption (the CLIP tokenizer lower-cases and collapses whitespace: 'a' / 'A', the -1 edit at every
+    even position, a space next to a space) is not computed again: its slot gets the no-op edit and the first occurrence's loss is
+    copied into it (leaf_amd/attacks.py: ``lend_duplicates``).  The target of a caption is its anchor row under ``objective``, or,
+    with ``class_features`` (unit rows [C, D]), its label (host int) under the classification margin loss
+    (``score_candidates_cls``): the predicted classes then come back with the losses, duplicates copying both."""
 
     def __init__(self, model, objective, dedupe, stats, class_features=None):
         self.model = model
-        self.objective = objective
-        self.class_features = class_features      # classification mode: ``loss`` takes the captions' labels in the anchors' place
         self.reuse = hasattr(model, "encode_text_kv") and getattr(model, "trim_rows", False)
         self.dedupe = dedupe and self.reuse
         self.stats = stats
+        if class_features is None:
+            self._score = lambda toks, target_g, R, **kw: (
+                model.score_candidates(toks, target_g, R, objective, want_features=False, want_loss=True, **kw)[2], None)
+        else:
+            self._score = lambda toks, target_g, R, **kw: model.score_candidates_cls(toks, class_features, target_g, R, **kw)[2:4]
 
     def kv(self, base, slot):
         return self.model.encode_text_kv(base, slot=slot) if self.reuse else None
 
-    def _score(self, toks, target_g, R, lens, pl, kv):
-        if self.class_features is None:
-            _, _, loss = self.model.score_candidates(toks, target_g, R, self.objective, want_features=False, want_loss=True,
-                                                     seq_lens=lens, prefix_lens=pl, kv=kv)
-            return loss, None
-        _, _, loss, pred, _ = self.model.score_candidates_cls(toks, self.class_features, target_g, R, seq_lens=lens, prefix_lens=pl, kv=kv)
-        return loss, pred
-
-    def loss(self, toks, lens, base, kv, anchor_g, R, count):
+    def loss(self, toks, lens, base, kv, target_g, R, count):
         import torch
-        Bg = len(anchor_g)
-        pl = None
-        if self.reuse:
-            neq = toks.reshape(Bg, R, -1) != base[:, None, :]
-            first = neq.argmax(-1)
-            first[~neq.any(-1)] = toks.shape[-1]
-            pl = first.reshape(-1)
+        Bg = len(target_g)
+        pl = first_difference(toks, base, R) if self.reuse else None
         dup = duplicate_map(toks, Bg, R) if self.dedupe else None
         is_dup = None if dup is None else (dup != np.arange(R)[None, :])
         if self.stats is not None:
@@ -213,26 +203,18 @@ class _Scorer:
             self.stats["full_rows"] = self.stats.get("full_rows", 0) + int(
                 (lens if lens is not None else toks.reshape(Bg * R, -1).argmax(-1) + 1).reshape(Bg, R)[real].sum())
             rows0 = self.model.rows_scored
-        if is_dup is not None and is_dup.any():
-            flat = is_dup.reshape(-1)
-            toks = toks.copy().reshape(Bg * R, -1)
-            rep = np.repeat(np.arange(Bg), R)[flat]
-            toks[flat] = base[rep]
-            if lens is not None:
-                lens = lens.copy()
-                lens[flat] = (base.argmax(-1) + 1)[rep]
-            pl = pl.copy()
-            pl[flat] = toks.shape[-1]                    # nothing differs from the clean caption: one row under prefix reuse
-            loss, pred = self._score(toks, anchor_g, R, lens, pl, kv)
-            dup_dev = torch.from_numpy(dup.astype(np.int64)).pin_memory().to(loss.device, non_blocking=True)
+        lent = is_dup is not None and is_dup.any()
+        if lent:
+            toks, lens, pl = lend_duplicates(toks, lens, pl, base, dup)
+        loss, pred = self._score(toks, target_g, R, seq_lens=lens, prefix_lens=pl, kv=kv)
+        if lent:
+            dup_dev = torch.from_numpy(dup).pin_memory().to(loss.device, non_blocking=True)
             loss = loss.gather(1, dup_dev)
             if pred is not None:
                 pred = pred.gather(1, dup_dev)
-        else:
-            loss, pred = self._score(toks, anchor_g, R, lens, pl, kv)
         if self.stats is not None:
             self.stats["computed_rows"] = self.stats.get("computed_rows", 0) + (self.model.rows_scored - rows0)
-        return loss if self.class_features is None else (loss, pred)
+        return loss, pred
 
 
 def _to_host(t):
@@ -280,6 +262,93 @@ def _prepare_anchor(anchor_features, objective):
 
 
 # ----------------------------------------------------------------------------- batched attacks
+def _charmer_edits(scorer, tokenizer, sentences, target_of, n, k, V, constrain, pipeline, max_rows, after_edit, stop_idle,
+                   return_trace, return_losses, return_picks, return_preds=None):
+    """Up to ``k`` Charmer edits on the captions that are active (at first: the non-empty ones).  ``target_of(g)``: what
+    ``scorer.loss`` compares the captions ``g`` (indices into the batch) with.  ``after_edit(sentences, picks)`` -> the captions of
+    the next edit, ``picks[b]`` being the predicted class of caption b's pick (None from a scorer without classes; captions
+    without a pick are absent); with ``stop_idle`` the loop ends when that set is empty.  Returns (sentences, edits received per
+    caption)."""
+    sentences = list(sentences)
+    B = len(sentences)
+    if pipeline is None:
+        pipeline = 2 if (scorer.reuse and B >= 64) else 1
+    nv = len(V)
+    received = [0] * B
+    active = [b for b, S in enumerate(sentences) if len(S) > 0]
+    for _ in range(k):
+        if stop_idle and not active:
+            break
+        groups = _groups(active, pipeline, lambda b: max(2 * len(sentences[b]), min(n, 2 * len(sentences[b])) * nv), max_rows)
+        base_all = tokenizer.encode_batch(sentences) if scorer.reuse else None
+        st1 = []
+        for gi, g in enumerate(groups):
+            sg = [sentences[b] for b in g]
+            base = base_all[g] if scorer.reuse else None
+            kv = scorer.kv(base, gi)          # the clean captions once per edit: their K/V serve both stages
+            z, c, count = stage1_plan(sg)
+            R = z.shape[1]
+            if R > SCORE_MAX_COLUMNS:
+                raise ValueError(f"a caption of {max(map(len, sg))} characters: stage 1 has {R} candidates, more than the "
+                                 f"{SCORE_MAX_COLUMNS} per caption one scoring launch takes")
+            toks, lens = prepare_stage(tokenizer, sg, z, c, constrain)
+            target_g = target_of(g)
+            loss, _ = scorer.loss(toks, lens, base, kv, target_g, R, count)
+            idx, _ = select_topk(loss, count, n)
+            st1.append((sg, base, kv, target_g, z, c, count, _to_host(idx), _to_host(loss) if return_losses is not None else None))
+        st2 = []
+        for sg, base, kv, target_g, z1, c1, count1, fin, fin_loss in st1:
+            top = fin()
+            m = np.minimum(n, count1)
+            st1_out = (render_plan(sg, z1, c1, count1) if return_trace is not None else None,
+                       [fin_loss()[i, :count1[i]] for i in range(len(sg))] if fin_loss is not None else None,
+                       [top[i, :m[i]] for i in range(len(sg))])
+            z, c, count = stage2_plan(top, m, V)
+            R = z.shape[1]
+            if R > SCORE_MAX_COLUMNS:
+                raise ValueError(f"stage 2 has {R} = n |V| candidates per caption, more than the {SCORE_MAX_COLUMNS} one scoring "
+                                 f"launch takes: lower n")
+            toks, lens = prepare_stage(tokenizer, sg, z, c, constrain)
+            loss, pred = scorer.loss(toks, lens, base, kv, target_g, R, count)
+            idx, _ = select_topk(loss, count, 1)
+            # the predicted class of the pick (a row without one: unused)
+            fin_pred = _to_host(pred.gather(1, idx.clamp(min=0).long())) if pred is not None else None
+            st2.append((sg, z, c, count, _to_host(idx), fin_pred, _to_host(loss) if return_losses is not None else None, st1_out))
+        # hooks: one entry per stage, captions in input order (captions that sat out: empty entries)
+        trace1, trace2 = ([[] for _ in range(B)] for _ in range(2))
+        loss1, loss2 = ([np.zeros(0, np.float32) for _ in range(B)] for _ in range(2))
+        pick1, pick2 = ([np.zeros(0, np.int64) for _ in range(B)] for _ in range(2))
+        preds = [None] * B
+        picks = {}
+        for g, (sg, z, c, count, fin, fin_pred, fin_loss, st1_out) in zip(groups, st2):
+            best = fin()[:, 0]
+            bpred = fin_pred()[:, 0] if fin_pred is not None else None
+            lh = fin_loss() if fin_loss is not None else None
+            strings = render_plan(sg, z, c, count) if return_trace is not None else None
+            for i, b in enumerate(g):
+                j = int(best[i])
+                if j >= 0:
+                    sentences[b] = _apply_edit(sg[i], int(z[i, j]), int(c[i, j]))
+                    received[b] += 1
+                    picks[b] = preds[b] = int(bpred[i]) if bpred is not None else None
+                if st1_out[0] is not None:
+                    trace1[b], trace2[b] = st1_out[0][i], strings[i]
+                if st1_out[1] is not None:
+                    loss1[b], loss2[b] = st1_out[1][i], lh[i, :count[i]]
+                pick1[b] = st1_out[2][i]
+                pick2[b] = np.array([j] if j >= 0 else [], dtype=np.int64)
+        if return_trace is not None:
+            return_trace += [trace1, trace2]
+        if return_losses is not None:
+            return_losses += [loss1, loss2]
+        if return_picks is not None:
+            return_picks += [pick1, pick2]
+        if return_preds is not None:
+            return_preds.append(preds)
+        active = after_edit(sentences, picks)
+    return sentences, received
+
+
 def attack_text_charmer(model, tokenizer, sentences, anchor_features, objective: str = "l2", n: int = 10, k: int = 1, V=DEFAULT_V,
                         constrain: bool = False, debug: bool = False, dedupe: bool = True, pipeline: Optional[int] = None,
                         max_rows: int = 65536, return_trace: Optional[list] = None, return_losses: Optional[list] = None,
@@ -295,87 +364,17 @@ def attack_text_charmer(model, tokenizer, sentences, anchor_features, objective:
     loss rows (numpy, [count[b]] per caption), ``return_picks`` per stage the picked columns per caption, ``stats`` candidate / row
     counts (duplicates skipped, rows computed under prefix reuse)."""
     import torch
-    sentences = list(sentences)
-    B = len(sentences)
     anchor_features = _prepare_anchor(anchor_features, objective)
-    scorer = _Scorer(model, objective, dedupe, stats)
-    if pipeline is None:
-        pipeline = 2 if (scorer.reuse and B >= 64) else 1
-    nv = len(V)
-    for _ in range(k):
-        active = [b for b, S in enumerate(sentences) if len(S) > 0]
-        groups = _groups(active, pipeline, lambda b: max(2 * len(sentences[b]), min(n, 2 * len(sentences[b])) * nv), max_rows)
-        base_all = tokenizer.encode_batch(sentences) if scorer.reuse else None
-        st1 = []
-        for gi, g in enumerate(groups):
-            sg = [sentences[b] for b in g]
-            base = base_all[g] if scorer.reuse else None
-            kv = scorer.kv(base, gi)          # the clean captions once per edit: their K/V serve both stages
-            z, c, count = stage1_plan(sg)
-            R = z.shape[1]
-            if R > SCORE_MAX_COLUMNS:
-                raise ValueError(f"a caption of {max(map(len, sg))} characters: stage 1 has {R} candidates, more than the "
-                                 f"{SCORE_MAX_COLUMNS} per caption one scoring launch takes")
-            toks, lens = prepare_stage(tokenizer, sg, z, c, constrain)
-            anchor_g = anchor_features[torch.as_tensor(g, device=anchor_features.device)]
-            loss = scorer.loss(toks, lens, base, kv, anchor_g, R, count)
-            idx, _ = select_topk(loss, count, n)
-            fin_loss = _to_host(loss) if return_losses is not None else None
-            st1.append((sg, base, kv, anchor_g, z, c, count, _to_host(idx), fin_loss))
-        st2 = []
-        for sg, base, kv, anchor_g, z1, c1, count1, fin, fin_loss in st1:
-            top = fin()
-            if return_trace is not None or return_losses is not None or return_picks is not None:
-                st1_out = (render_plan(sg, z1, c1, count1) if return_trace is not None else None,
-                           [fin_loss()[b, :count1[b]] for b in range(len(sg))] if fin_loss is not None else None,
-                           [top[b, :min(n, count1[b])] for b in range(len(sg))])
-            else:
-                st1_out = None
-            m = np.minimum(n, count1)
-            z, c, count = stage2_plan(top, m, V)
-            R = z.shape[1]
-            if R > SCORE_MAX_COLUMNS:
-                raise ValueError(f"stage 2 has {R} = n |V| candidates per caption, more than the {SCORE_MAX_COLUMNS} one scoring "
-                                 f"launch takes: lower n")
-            toks, lens = prepare_stage(tokenizer, sg, z, c, constrain)
-            loss = scorer.loss(toks, lens, base, kv, anchor_g, R, count)
-            idx, _ = select_topk(loss, count, 1)
-            st2.append((sg, z, c, count, _to_host(idx), _to_host(loss) if return_losses is not None else None, st1_out))
-        # hooks: one entry per stage, captions in input order (empty captions: empty lists)
-        trace1, trace2 = ([[] for _ in range(B)] for _ in range(2))
-        loss1, loss2 = ([np.zeros(0, np.float32) for _ in range(B)] for _ in range(2))
-        pick1, pick2 = ([np.zeros(0, np.int64) for _ in range(B)] for _ in range(2))
-        new = list(sentences)
-        for g, (sg, z, c, count, fin, fin_loss, st1_out) in zip(groups, st2):
-            best = fin()[:, 0]
-            for i, b in enumerate(g):
-                j = int(best[i])
-                if j >= 0:
-                    new[b] = _apply_edit(sg[i], int(z[i, j]), int(c[i, j]))
-                if st1_out is not None:
-                    if st1_out[0] is not None:
-                        trace1[b] = st1_out[0][i]
-                    if st1_out[1] is not None:
-                        loss1[b] = st1_out[1][i]
-                    pick1[b] = st1_out[2][i]
-                    pick2[b] = np.array([j] if j >= 0 else [], dtype=np.int64)
-            if return_trace is not None:
-                for i, s in enumerate(render_plan(sg, z, c, count)):
-                    trace2[g[i]] = s
-            if fin_loss is not None:
-                lh = fin_loss()
-                for i, b in enumerate(g):
-                    loss2[b] = lh[i, :count[i]]
-        if return_trace is not None:
-            return_trace += [trace1, trace2]
-        if return_losses is not None:
-            return_losses += [loss1, loss2]
-        if return_picks is not None:
-            return_picks += [pick1, pick2]
-        sentences = new
-        if debug and B:
+
+    def after_edit(sentences, picks):          # every non-empty caption takes every edit
+        if debug and sentences:
             print(sentences[0])
-    return sentences, [max(k, 1)] * B
+        return [b for b, S in enumerate(sentences) if len(S) > 0]
+
+    sentences, _ = _charmer_edits(_Scorer(model, objective, dedupe, stats), tokenizer, sentences,
+                                  lambda g: anchor_features[torch.as_tensor(g, device=anchor_features.device)], n, k, V, constrain,
+                                  pipeline, max_rows, after_edit, False, return_trace, return_losses, return_picks)
+    return sentences, [max(k, 1)] * len(sentences)
 
 
 def attack_text_charmer_classification_batched(model, tokenizer, sentences, class_features, labels, n: int = 10, k: int = 1, V=DEFAULT_V,
@@ -402,89 +401,16 @@ def attack_text_charmer_classification_batched(model, tokenizer, sentences, clas
     Hooks as in ``attack_text_charmer`` (two entries per edit; a caption that has stopped has empty entries); ``return_preds``
     receives per edit the predicted class of each caption's pick (None for a caption that did not take part).  ``scorer``: a test
     seam, an object with ``reuse`` / ``kv`` / ``loss`` like ``_Scorer`` in classification mode."""
-    import torch
     sentences = list(sentences)
-    B = len(sentences)
     labels = np.asarray(labels, dtype=np.int64).reshape(-1)
-    if labels.size != B:
-        raise ValueError(f"{labels.size} labels for {B} sentences")
+    if labels.size != len(sentences):
+        raise ValueError(f"{labels.size} labels for {len(sentences)} sentences")
     if scorer is None:
         scorer = _Scorer(model, None, dedupe, stats, class_features=class_features)
-    if pipeline is None:
-        pipeline = 2 if (scorer.reuse and B >= 64) else 1
-    nv = len(V)
-    dists = [0] * B
-    active = [b for b, S in enumerate(sentences) if len(S) > 0]
-    for _ in range(k):
-        if not active:
-            break
-        groups = _groups(active, pipeline, lambda b: max(2 * len(sentences[b]), min(n, 2 * len(sentences[b])) * nv), max_rows)
-        base_all = tokenizer.encode_batch(sentences) if scorer.reuse else None
-        st1 = []
-        for gi, g in enumerate(groups):
-            sg = [sentences[b] for b in g]
-            base = base_all[g] if scorer.reuse else None
-            kv = scorer.kv(base, gi)          # the clean captions once per edit: their K/V serve both stages
-            z, c, count = stage1_plan(sg)
-            R = z.shape[1]
-            if R > SCORE_MAX_COLUMNS:
-                raise ValueError(f"a caption of {max(map(len, sg))} characters: stage 1 has {R} candidates, more than the "
-                                 f"{SCORE_MAX_COLUMNS} per caption one scoring launch takes")
-            toks, lens = prepare_stage(tokenizer, sg, z, c, False)
-            loss, _ = scorer.loss(toks, lens, base, kv, labels[g], R, count)
-            idx, _ = select_topk(loss, count, n)
-            st1.append((sg, base, kv, z, c, count, _to_host(idx), _to_host(loss) if return_losses is not None else None))
-        st2 = []
-        for g, (sg, base, kv, z1, c1, count1, fin, fin_loss) in zip(groups, st1):
-            top = fin()
-            m = np.minimum(n, count1)
-            st1_out = (render_plan(sg, z1, c1, count1) if return_trace is not None else None,
-                       [fin_loss()[i, :count1[i]] for i in range(len(sg))] if fin_loss is not None else None,
-                       [top[i, :m[i]] for i in range(len(sg))])
-            z, c, count = stage2_plan(top, m, V)
-            R = z.shape[1]
-            if R > SCORE_MAX_COLUMNS:
-                raise ValueError(f"stage 2 has {R} = n |V| candidates per caption, more than the {SCORE_MAX_COLUMNS} one scoring "
-                                 f"launch takes: lower n")
-            toks, lens = prepare_stage(tokenizer, sg, z, c, False)
-            loss, pred = scorer.loss(toks, lens, base, kv, labels[g], R, count)
-            idx, _ = select_topk(loss, count, 1)
-            pick_pred = pred.gather(1, idx.clamp(min=0).long())          # the predicted class of the pick (a row without one: unused)
-            st2.append((sg, z, c, count, _to_host(idx), _to_host(pick_pred), _to_host(loss) if return_losses is not None else None,
-                        st1_out))
-        trace1, trace2 = ([[] for _ in range(B)] for _ in range(2))
-        loss1, loss2 = ([np.zeros(0, np.float32) for _ in range(B)] for _ in range(2))
-        pick1, pick2 = ([np.zeros(0, np.int64) for _ in range(B)] for _ in range(2))
-        preds = [None] * B
-        still = []
-        for g, (sg, z, c, count, fin, fin_pred, fin_loss, st1_out) in zip(groups, st2):
-            best, bpred = fin()[:, 0], fin_pred()[:, 0]
-            lh = fin_loss() if fin_loss is not None else None
-            strings = render_plan(sg, z, c, count) if return_trace is not None else None
-            for i, b in enumerate(g):
-                j = int(best[i])
-                if j >= 0:
-                    sentences[b] = _apply_edit(sg[i], int(z[i, j]), int(c[i, j]))
-                    dists[b] += 1
-                    preds[b] = int(bpred[i])
-                    if preds[b] == labels[b]:
-                        still.append(b)               # still classified as its label: it takes the next edit
-                if st1_out[0] is not None:
-                    trace1[b], trace2[b] = st1_out[0][i], strings[i]
-                if st1_out[1] is not None:
-                    loss1[b], loss2[b] = st1_out[1][i], lh[i, :count[i]]
-                pick1[b] = st1_out[2][i]
-                pick2[b] = np.array([j] if j >= 0 else [], dtype=np.int64)
-        if return_trace is not None:
-            return_trace += [trace1, trace2]
-        if return_losses is not None:
-            return_losses += [loss1, loss2]
-        if return_picks is not None:
-            return_picks += [pick1, pick2]
-        if return_preds is not None:
-            return_preds.append(preds)
-        active = still
-    return sentences, dists
+    # a caption takes the next edit while its pick is still classified as its label; one without a pick leaves too
+    return _charmer_edits(scorer, tokenizer, sentences, lambda g: labels[g], n, k, V, False, pipeline, max_rows,
+                          lambda sentences, picks: [b for b, p in picks.items() if p == labels[b]], True,
+                          return_trace, return_losses, return_picks, return_preds)
 
 
 def attack_text_bruteforce_batched(model, tokenizer, sentences, anchor_features, objective: str = "l2", V=DEFAULT_V,
@@ -520,7 +446,7 @@ def attack_text_bruteforce_batched(model, tokenizer, sentences, anchor_features,
             width = min(chunk_cols, max(tmax - c0, 1))
             z, c, count = bruteforce_plan(sg, V, c0, width)
             toks, lens = prepare_stage(tokenizer, sg, z, c, constrain)
-            loss = scorer.loss(toks, lens, base, kv, anchor_g, width, count)
+            loss, _ = scorer.loss(toks, lens, base, kv, anchor_g, width, count)
             select_topk(loss, count, 1, col_offset=c0, accumulate=True, out=acc)
             plans.append((c0, z, c, count))
             if return_losses is not None:

@@ -76,6 +76,51 @@ def _ptr(t: Optional[torch.Tensor]):
     return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
 
 
+def _host_lens(tokens) -> np.ndarray:
+    """kept length per token row, EOT position + 1 (EOT is the largest id); device-resident tokens are copied to the host"""
+    arr = tokens if isinstance(tokens, np.ndarray) else tokens.cpu().numpy()
+    return arr.reshape(-1, arr.shape[-1]).argmax(-1) + 1
+
+
+def _lens_cu(lens):
+    """(lens int32 [n], cu int32 [n + 1]: cu[i] = rows in front of sequence i) of host lengths, both contiguous"""
+    lens = np.ascontiguousarray(np.asarray(lens).reshape(-1), dtype=np.int32)
+    cu = np.zeros(lens.size + 1, dtype=np.int32)
+    np.cumsum(lens, out=cu[1:])
+    return lens, cu
+
+
+class _ScoreTarget:
+    """What a scoring pass compares its candidates with, the Python side of ``ScoreTarget`` in leaf_amd/csrc/api.hip: one anchor row
+    per caption under an objective, or (``class_feat`` given) a class matrix shared by all captions with a label per caption and the
+    wanted extra outputs.  ``dense`` / ``prefix`` name the C entries of the two passes; ``bind`` makes their arguments."""
+
+    def __init__(self, anchor=None, objective="l2", class_feat=None, labels=None, want_pred=False, want_logits=False):
+        self.anchor, self.obj = anchor, _OBJ[objective]
+        self.class_feat, self.labels, self.want_pred, self.want_logits = class_feat, labels, want_pred, want_logits
+        if class_feat is None:
+            self.B, self.dense, self.prefix = int(anchor.shape[0]), "leaf_score_candidates", "leaf_score_candidates_prefix"
+        else:
+            self.B, self.dense, self.prefix = int(labels.shape[0]), "leaf_score_candidates_cls", "leaf_score_candidates_prefix_cls"
+
+    def bind(self, rho: int, embed_dim: int, want_features: bool, want_loss: bool):
+        """Output buffers of one pass over B * rho candidates.  Returns (the C arguments from the target to the last output, which
+        both entries of the target take in this order; what the scoring call returns)."""
+        B, dev = self.B, (self.anchor if self.class_feat is None else self.class_feat).device
+        idx = torch.empty(B, dtype=torch.int32, device=dev)
+        feat = torch.empty(B, embed_dim, dtype=torch.float32, device=dev) if want_features else None
+        if self.class_feat is None:
+            loss = torch.empty(B, rho, dtype=torch.float32, device=dev) if want_loss else None
+            return ((_ptr(self.anchor), B, rho, self.obj, _ptr(idx), _ptr(feat), _ptr(loss)),
+                    (idx, feat, loss) if want_loss else (idx, feat))
+        n_cls = int(self.class_feat.shape[0])
+        loss = torch.empty(B, rho, dtype=torch.float32, device=dev)          # always: the pass takes best_idx from it
+        pred = torch.empty(B, rho, dtype=torch.int32, device=dev) if self.want_pred else None
+        logits = torch.empty(B * rho, n_cls, dtype=torch.float32, device=dev) if self.want_logits else None
+        return ((_ptr(self.class_feat), n_cls, _ptr(self.labels), B, rho, _ptr(idx), _ptr(feat), _ptr(loss), _ptr(pred), _ptr(logits)),
+                (idx, feat, (loss if want_loss else None), pred, logits))
+
+
 def verify_single_edit(cand_tokens, cand_lens, prefix, base_tokens, base_lens, rho: int) -> None:
     """The promise of a ``single_edit`` scoring pass, checked on the tokens (``LEAF_VERIFY_SINGLE_EDIT=1``; tests and debugging: the
     comparison needs the tokens on the host): candidate ``i`` belongs to caption ``i // rho``, has the caption's length, and differs
@@ -142,13 +187,13 @@ class LeafCLIPText:
         # tensors of a loaded checkpoint outside the text tower (visual.*, ...): kept on the host and written back by
         # state_dict(), so that epoch_latest.pt stays a FULL CLIP state_dict the reference's --resume / converters can load
         self.extra_state: Dict[str, torch.Tensor] = {}
-        self._ws: Dict[int, torch.Tensor] = {}
+        self._buf: Dict[object, torch.Tensor] = {}      # device byte buffers that grow on demand (_grow): workspaces, K/V slots, stash
         self._packed = False
         # exact work skipping: compute only rows up to EOT (include/leaf_hip.h, "EOT trimming"); LEAF_PACK=0 disables
         self.trim_rows = os.environ.get("LEAF_PACK", "1") != "0"
         self.training = False
         # training state (allocated on demand)
-        self.grads = self.exp_avg = self.exp_avg_sq = self.w16_bwd = self._stash = None
+        self.grads = self.exp_avg = self.exp_avg_sq = self.w16_bwd = None
         self.opt_step = 0
         self.rows_scored = 0      # packed rows handed to the scoring passes so far (host-side count; bench.py reports it per rank)
         if trainable:
@@ -205,16 +250,21 @@ class LeafCLIPText:
     def _stream(self):
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
-    def _workspace(self, mode: int, n_seq: int) -> torch.Tensor:
-        need = self._lib.leaf_text_workspace_bytes(self._h, n_seq, mode)
-        ws = self._ws.get(mode)
-        if ws is None or ws.numel() < need:
-            ws = None
-            self._ws[mode] = None
+    def _grow(self, key, need: int) -> torch.Tensor:
+        """the device byte buffer ``key``, allocated anew when it holds fewer than ``need`` bytes (the old one is dropped first)"""
+        buf = self._buf.get(key)
+        if buf is None or buf.numel() < need:
+            buf = self._buf[key] = None
             with torch.cuda.device(self.device):
-                ws = torch.empty(need, dtype=torch.uint8, device=self.device)
-            self._ws[mode] = ws
-        return ws
+                buf = self._buf[key] = torch.empty(need, dtype=torch.uint8, device=self.device)
+        return buf
+
+    def _workspace(self, mode: int, n_seq: int) -> torch.Tensor:
+        return self._grow(("ws", mode), self._lib.leaf_text_workspace_bytes(self._h, n_seq, mode))
+
+    def _kv_buffer(self, slot: int, rows: int) -> torch.Tensor:
+        """cache buffer ``slot`` for the per-layer 16-bit q|k|v rows of ``rows`` caption rows"""
+        return self._grow(("kv", slot), max(rows * 3 * self.cfg.width * 2 * self.cfg.layers, 1))
 
     # ------------------------------------------------------------------ weights
     def init_random(self, seed: int = 1):
@@ -368,15 +418,10 @@ class LeafCLIPText:
         if not self.trim_rows:
             return C.c_void_p(0), None, None
         if seq_lens is None:
-            if isinstance(text, np.ndarray):
-                seq_lens = text.reshape(-1, text.shape[-1]).argmax(-1) + 1
-            elif isinstance(text, torch.Tensor) and text.device.type == "cpu":
-                seq_lens = (text.reshape(-1, text.shape[-1]).argmax(-1) + 1).numpy()
-            else:
+            if not isinstance(text, np.ndarray) and not (isinstance(text, torch.Tensor) and text.device.type == "cpu"):
                 return C.c_void_p(0), None, None       # device-resident tokens, lengths unknown on the host
-        lens = np.ascontiguousarray(np.asarray(seq_lens).reshape(-1), dtype=np.int32)
-        cu = np.zeros(lens.size + 1, dtype=np.int32)
-        np.cumsum(lens, out=cu[1:])
+            seq_lens = _host_lens(text)
+        lens, cu = _lens_cu(seq_lens)
         # pinned + non_blocking: a pageable H2D copy would make the host wait for all queued GPU work
         return C.c_void_p(lens.ctypes.data), torch.from_numpy(cu).pin_memory().to(self.device, non_blocking=True), lens
 
@@ -394,12 +439,7 @@ class LeafCLIPText:
             t = self._tokens(text)
             n = t.shape[0]
             out = torch.empty(n, self.cfg.embed_dim, dtype=torch.float32, device=self.device)
-            need = self._lib.leaf_text_precise_workspace_bytes(self._h, n)
-            ws = self._ws.get("precise")
-            if ws is None or ws.numel() < need:
-                self._ws["precise"] = ws = None
-                with torch.cuda.device(self.device):
-                    self._ws["precise"] = ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+            ws = self._grow(("ws", "precise"), self._lib.leaf_text_precise_workspace_bytes(self._h, n))
             _lib.check(self._lib.leaf_text_forward_precise(self._h, _ptr(self.flat), _ptr(t), lens_p, _ptr(cu), n, _ptr(out),
                                                            int(bool(normalize)), _ptr(ws), ws.numel(), self._stream()),
                        "leaf_text_forward_precise")
@@ -423,29 +463,11 @@ class LeafCLIPText:
         groups of captions, leaf_amd/attacks.py)."""
         if not self._packed:
             self.pack()
-        if seq_lens is None:
-            arr = text if isinstance(text, np.ndarray) else text.cpu().numpy()
-            seq_lens = arr.reshape(-1, arr.shape[-1]).argmax(-1) + 1
-        lens = np.ascontiguousarray(np.asarray(seq_lens).reshape(-1), dtype=np.int32)
-        cu = np.zeros(lens.size + 1, dtype=np.int32)
-        np.cumsum(lens, out=cu[1:])
+        lens, cu = _lens_cu(_host_lens(text) if seq_lens is None else seq_lens)
         cu_dev = torch.from_numpy(cu).pin_memory().to(self.device, non_blocking=True)
         t = self._tokens(text)
         n = t.shape[0]
-        need = int(cu[-1]) * 3 * self.cfg.width * 2 * self.cfg.layers
-        if slot == 0:
-            if getattr(self, "_kv", None) is None or self._kv.numel() < need:
-                self._kv = None
-                with torch.cuda.device(self.device):
-                    self._kv = torch.empty(max(need, 1), dtype=torch.uint8, device=self.device)
-            kvbuf = self._kv
-        else:
-            slots = self.__dict__.setdefault("_kv_slots", {})
-            if slots.get(slot) is None or slots[slot].numel() < need:
-                slots[slot] = None
-                with torch.cuda.device(self.device):
-                    slots[slot] = torch.empty(max(need, 1), dtype=torch.uint8, device=self.device)
-            kvbuf = slots[slot]
+        kvbuf = self._kv_buffer(slot, int(cu[-1]))
         out = torch.empty(n, self.cfg.embed_dim, dtype=torch.float32, device=self.device) if want_features else None
         ws = self._workspace(0, n)
         _lib.check(self._lib.leaf_text_forward_kv(self._h, _ptr(self.flat), _ptr(self.w16), _ptr(t),
@@ -459,7 +481,10 @@ class LeafCLIPText:
 
     def score_candidates(self, tokens, anchor: torch.Tensor, rho: int, objective: str = "l2", want_features=True,
                          want_loss=False, seq_lens=None, prefix_lens=None, kv=None, single_edit: bool = False):
-        """``prefix_lens`` (host int array [B*rho], number of leading positions equal to the clean caption) together
+        """tokens [B*rho, ctx] (or [B,rho,ctx]); anchor [B,D] fp32 CUDA.  Returns (best_idx int32[B],
+        best_feat [B,D] or None) (+ loss [B,rho] when want_loss).
+
+        ``prefix_lens`` (host int array [B*rho], number of leading positions equal to the clean caption) together
         with ``kv`` (from ``encode_text_kv`` of the clean captions) enables prefix reuse: only positions from the
         first changed token on are recomputed.  ``seq_lens`` must then be the candidates' full lengths.
 
@@ -470,46 +495,43 @@ class LeafCLIPText:
         ``charmer``, where a character edit re-tokenises the rest of the caption.  ``LEAF_VERIFY_SINGLE_EDIT=1`` checks the promise
         against the tokens (a device-to-host copy)."""
         if prefix_lens is not None and kv is not None and self.trim_rows:
-            return self._score_prefix(tokens, anchor, rho, objective, want_features, want_loss, seq_lens, prefix_lens, kv, single_edit)
-        """tokens [B*rho, ctx] (or [B,rho,ctx]); anchor [B,D] fp32 CUDA.  Returns (best_idx int32[B],
-        best_feat [B,D] or None) (+ loss [B,rho] when want_loss)."""
+            return self.score_candidates_run(self.score_candidates_prepare(tokens, anchor, rho, objective, want_features, want_loss,
+                                                                           seq_lens=seq_lens, kv=kv, single_edit=single_edit), prefix_lens)
+        return self._score_dense(self._anchor_target(anchor, objective), tokens, rho, want_features, want_loss, seq_lens)
+
+    def _anchor_target(self, anchor, objective):
+        return _ScoreTarget(anchor.to(device=self.device, dtype=torch.float32).contiguous(), objective)
+
+    def _score_dense(self, target, tokens, rho, want_features, want_loss, seq_lens):
+        """one pass over all kept rows of the B * rho candidates, scored against ``target``"""
         if not self._packed:
             self.pack()
         lens_p, cu, keep = self._row_plan(tokens, seq_lens)
         if isinstance(tokens, np.ndarray):
             tokens = torch.from_numpy(tokens)
         t = self._tokens(tokens.reshape(-1, tokens.shape[-1]))
-        B = anchor.shape[0]
+        B = target.B
         if t.shape[0] != B * rho:
             raise ValueError(f"{t.shape[0]} candidate rows != B*rho = {B}*{rho}")
-        anchor = anchor.to(device=self.device, dtype=torch.float32).contiguous()
-        idx = torch.empty(B, dtype=torch.int32, device=self.device)
-        feat = torch.empty(B, self.cfg.embed_dim, dtype=torch.float32, device=self.device) if want_features else None
-        loss = torch.empty(B, rho, dtype=torch.float32, device=self.device) if want_loss else None
+        args, ret = target.bind(rho, self.cfg.embed_dim, want_features, want_loss)
         ws = self._workspace(1, B * rho)
         self.rows_scored += int(keep.sum()) if keep is not None else B * rho * self.cfg.context_length
-        _lib.check(self._lib.leaf_score_candidates(self._h, _ptr(self.flat), _ptr(self.w16), _ptr(t), lens_p, _ptr(cu),
-                                                   _ptr(anchor), B, rho, _OBJ[objective], _ptr(idx), _ptr(feat),
-                                                   _ptr(loss), _ptr(ws), ws.numel(), self._stream()),
-                   "leaf_score_candidates")
-        return (idx, feat, loss) if want_loss else (idx, feat)
-
-    def _score_prefix(self, tokens, anchor, rho, objective, want_features, want_loss, seq_lens, prefix_lens, kv, single_edit=False):
-        return self.score_candidates_run(
-            self.score_candidates_prepare(tokens, anchor, rho, objective, want_features, want_loss, seq_lens, kv, single_edit), prefix_lens)
+        _lib.check(getattr(self._lib, target.dense)(self._h, _ptr(self.flat), _ptr(self.w16), _ptr(t), lens_p, _ptr(cu), *args,
+                                                    _ptr(ws), ws.numel(), self._stream()), target.dense)
+        return ret
 
     def score_candidates_prepare(self, tokens, anchor, rho, objective="l2", want_features=True, want_loss=False, seq_lens=None, kv=None,
                                  single_edit: bool = False, cls=None):
         """Everything of a prefix-reuse ``score_candidates`` call that does NOT depend on the prefix lengths: token / anchor placement,
-        output buffers, the length limits and a pinned staging buffer for the row plan.  The search calls this BEFORE it waits for the
-        previous stage's winners and ``score_candidates_run(plan, prefix_lens)`` right after them: the device idles at that boundary
-        for as long as the host needs between the two (round 4, tools/stage_hole_probe.py: 270 -> 94 us at ViT-L B = 128, 181 -> 123 us at ViT-H
-        B = 32).  ``cls`` (from ``_cls_target``; ``anchor`` is then None): score against a class matrix, ``score_candidates_cls``."""
+        output buffers, the length limits, a pinned staging buffer for the row plan, the C entry and its arguments known by now.  The
+        search calls this BEFORE it waits for the previous stage's winners and ``score_candidates_run(plan, prefix_lens)`` right after
+        them: the device idles at that boundary for as long as the host needs between the two (round 4, tools/stage_hole_probe.py:
+        270 -> 94 us at ViT-L B = 128, 181 -> 123 us at ViT-H B = 32).  ``cls`` (from ``_cls_target``; ``anchor`` is then None): score against a class matrix, ``score_candidates_cls``."""
         if not self._packed:
             self.pack()
+        target = cls if cls is not None else self._anchor_target(anchor, objective)
         if seq_lens is None:
-            arr = tokens if isinstance(tokens, np.ndarray) else tokens.cpu().numpy()
-            seq_lens = arr.reshape(-1, arr.shape[-1]).argmax(-1) + 1
+            seq_lens = _host_lens(tokens)
         full = np.ascontiguousarray(np.asarray(seq_lens).reshape(-1), dtype=np.int32)
         n = full.size
         # prefix <= full - 1 (keep at least the EOT row) and <= the rows the cache really holds
@@ -518,7 +540,7 @@ class LeafCLIPText:
         if isinstance(tokens, np.ndarray):
             tokens = torch.from_numpy(tokens)
         t = self._tokens(tokens.reshape(-1, tokens.shape[-1]))
-        B = anchor.shape[0] if cls is None else cls["B"]
+        B = target.B
         if t.shape[0] != B * rho or kv["n"] != B or n != B * rho:
             raise ValueError("candidate rows / kv cache do not match B*rho")
         if kv.get("arith", self.arithmetic_tag()) != self.arithmetic_tag():
@@ -531,18 +553,18 @@ class LeafCLIPText:
                                  "that did not run with single_edit): rebuild it with encode_text_kv or score_candidates_fused(single_edit=True)")
             if not np.array_equal(full, np.repeat(kv["lens"].astype(np.int32), rho)):
                 raise ValueError("single_edit pass: a candidate's length differs from its caption's")
-        if cls is None:
-            anchor = anchor.to(device=self.device, dtype=torch.float32).contiguous()
-        idx = torch.empty(B, dtype=torch.int32, device=self.device)
-        feat = torch.empty(B, self.cfg.embed_dim, dtype=torch.float32, device=self.device) if want_features else None
-        loss = torch.empty(B, rho, dtype=torch.float32, device=self.device) if (want_loss or cls is not None) else None
-        return {"full": full, "limit": limit, "host": host, "t": t, "anchor": anchor, "idx": idx, "feat": feat, "loss": loss, "B": B,
-                "rho": rho, "obj": _OBJ[objective], "kv": kv, "ws": self._workspace(1, B * rho), "max_len": int(full.max()),
-                "want_loss": want_loss, "single_edit": bool(single_edit), "cls": cls}
+        args, ret = target.bind(rho, self.cfg.embed_dim, want_features, want_loss)
+        ws = self._workspace(1, B * rho)
+        # head / tail: the C arguments in front of and behind the three that ``score_candidates_run`` computes
+        return {"full": full, "limit": limit, "host": host, "t": t, "rho": rho, "kv": kv, "single_edit": bool(single_edit),
+                "target": target, "ws": ws, "entry": target.prefix, "fn": getattr(self._lib, target.prefix),
+                "head": (self._h, _ptr(self.flat), _ptr(self.w16), _ptr(t)),
+                "tail": (_ptr(kv["base_cu"]), _ptr(kv["kv"]), kv["base_rows"], int(full.max()), *args, _ptr(ws), ws.numel()),
+                "ret": ret}
 
     def score_candidates_run(self, plan, prefix_lens):
         """The prefix-dependent rest of ``score_candidates_prepare``: row plan (suffix rows per candidate, their running sum), one
-        host-to-device copy, the launches.  Returns what ``score_candidates`` returns."""
+        host-to-device copy, the launches.  Returns what ``score_candidates`` (``score_candidates_cls``) returns."""
         full, n, kv = plan["full"], plan["full"].size, plan["kv"]
         hv = plan["host"].numpy()
         pfx = hv[n + 1:]
@@ -553,26 +575,14 @@ class LeafCLIPText:
         dev = plan["host"].to(self.device, non_blocking=True)
         cu_dev, pfx_dev = dev[:n + 1], dev[n + 1:]
         self.rows_scored += int(hv[n])
-        cls = plan.get("cls")
-        if cls is not None:
-            pred, logits = self._cls_outputs(cls, plan["B"], plan["rho"])
-            _lib.check(self._lib.leaf_score_candidates_prefix_cls(
-                self._h, _ptr(self.flat), _ptr(self.w16), _ptr(plan["t"]), C.c_void_p(suf.ctypes.data), _ptr(cu_dev), _ptr(pfx_dev),
-                _ptr(kv["base_cu"]), _ptr(kv["kv"]), kv["base_rows"], plan["max_len"], _ptr(cls["class_feat"]), cls["C"], _ptr(cls["labels"]),
-                plan["B"], plan["rho"], _ptr(plan["idx"]), _ptr(plan["feat"]), _ptr(plan["loss"]), _ptr(pred), _ptr(logits),
-                _ptr(plan["ws"]), plan["ws"].numel(), self._stream()), "leaf_score_candidates_prefix_cls")
-            return plan["idx"], plan["feat"], (plan["loss"] if plan["want_loss"] else None), pred, logits
-        single_edit = plan.get("single_edit", False)
+        single_edit = plan["single_edit"]
         if single_edit and os.environ.get("LEAF_VERIFY_SINGLE_EDIT") == "1":
             if kv.get("tokens") is None:
                 raise ValueError("LEAF_VERIFY_SINGLE_EDIT: the K/V cache does not carry its captions' tokens")
             verify_single_edit(plan["t"], full, pfx, kv["tokens"], kv["lens"], plan["rho"])
-        self._single_edit_call(single_edit, lambda: _lib.check(self._lib.leaf_score_candidates_prefix(
-            self._h, _ptr(self.flat), _ptr(self.w16), _ptr(plan["t"]), C.c_void_p(suf.ctypes.data), _ptr(cu_dev), _ptr(pfx_dev),
-            _ptr(kv["base_cu"]), _ptr(kv["kv"]), kv["base_rows"], plan["max_len"], _ptr(plan["anchor"]), plan["B"], plan["rho"], plan["obj"],
-            _ptr(plan["idx"]), _ptr(plan["feat"]), _ptr(plan["loss"]), _ptr(plan["ws"]), plan["ws"].numel(), self._stream()),
-            "leaf_score_candidates_prefix"))
-        return (plan["idx"], plan["feat"], plan["loss"]) if plan["want_loss"] else (plan["idx"], plan["feat"])
+        self._single_edit_call(single_edit, lambda: _lib.check(plan["fn"](
+            *plan["head"], C.c_void_p(suf.ctypes.data), _ptr(cu_dev), _ptr(pfx_dev), *plan["tail"], self._stream()), plan["entry"]))
+        return plan["ret"]
 
     # ------------------------------------------------------------------ classification scoring (classify.hip)
     def _cls_target(self, class_features, labels, want_pred, want_logits):
@@ -587,12 +597,7 @@ class LeafCLIPText:
         if lab.size and (lab.min() < 0 or lab.max() >= n_cls):
             raise ValueError(f"label outside [0, {n_cls}): {lab[(lab < 0) | (lab >= n_cls)][:4].tolist()}")
         lab_dev = torch.from_numpy(lab.astype(np.int32)).pin_memory().to(self.device, non_blocking=True)
-        return {"class_feat": cf, "C": n_cls, "labels": lab_dev, "B": int(lab.size), "want_pred": want_pred, "want_logits": want_logits}
-
-    def _cls_outputs(self, cls, B, rho):
-        pred = torch.empty(B, rho, dtype=torch.int32, device=self.device) if cls["want_pred"] else None
-        logits = torch.empty(B * rho, cls["C"], dtype=torch.float32, device=self.device) if cls["want_logits"] else None
-        return pred, logits
+        return _ScoreTarget(class_feat=cf, labels=lab_dev, want_pred=want_pred, want_logits=want_logits)
 
     def score_candidates_cls(self, tokens, class_features: torch.Tensor, labels, rho: int, want_features=False, want_loss=True,
                              want_pred=True, want_logits=False, seq_lens=None, prefix_lens=None, kv=None):
@@ -605,27 +610,8 @@ class LeafCLIPText:
         cls = self._cls_target(class_features, labels, want_pred, want_logits)
         if prefix_lens is not None and kv is not None and self.trim_rows:
             return self.score_candidates_run(
-                self.score_candidates_prepare(tokens, None, rho, "l2", want_features, want_loss, seq_lens, kv, cls=cls), prefix_lens)
-        if not self._packed:
-            self.pack()
-        lens_p, cu, keep = self._row_plan(tokens, seq_lens)
-        if isinstance(tokens, np.ndarray):
-            tokens = torch.from_numpy(tokens)
-        t = self._tokens(tokens.reshape(-1, tokens.shape[-1]))
-        B = cls["B"]
-        if t.shape[0] != B * rho:
-            raise ValueError(f"{t.shape[0]} candidate rows != B*rho = {B}*{rho}")
-        idx = torch.empty(B, dtype=torch.int32, device=self.device)
-        feat = torch.empty(B, self.cfg.embed_dim, dtype=torch.float32, device=self.device) if want_features else None
-        loss = torch.empty(B, rho, dtype=torch.float32, device=self.device)
-        pred, logits = self._cls_outputs(cls, B, rho)
-        ws = self._workspace(1, B * rho)
-        self.rows_scored += int(keep.sum()) if keep is not None else B * rho * self.cfg.context_length
-        _lib.check(self._lib.leaf_score_candidates_cls(self._h, _ptr(self.flat), _ptr(self.w16), _ptr(t), lens_p, _ptr(cu),
-                                                       _ptr(cls["class_feat"]), cls["C"], _ptr(cls["labels"]), B, rho, _ptr(idx),
-                                                       _ptr(feat), _ptr(loss), _ptr(pred), _ptr(logits), _ptr(ws), ws.numel(),
-                                                       self._stream()), "leaf_score_candidates_cls")
-        return idx, feat, (loss if want_loss else None), pred, logits
+                self.score_candidates_prepare(tokens, None, rho, "l2", want_features, want_loss, seq_lens=seq_lens, kv=kv, cls=cls), prefix_lens)
+        return self._score_dense(cls, tokens, rho, want_features, want_loss, seq_lens)
 
     def score_candidates_fused(self, base_tokens, base_lens, tokens, anchor: torch.Tensor, rho: int, seq_lens, prefix_lens,
                                objective: str = "l2", want_features: bool = False, want_loss: bool = False, single_edit: bool = False):
@@ -642,9 +628,7 @@ class LeafCLIPText:
         full = np.asarray(seq_lens, dtype=np.int64).reshape(-1)
         pfx = np.minimum(np.asarray(prefix_lens, dtype=np.int64).reshape(-1), full - 1)      # keep at least the EOT row
         pfx = np.minimum(pfx, np.repeat(blens.astype(np.int64), rho))                        # rows the captions really have
-        lens = np.ascontiguousarray(np.concatenate([blens, full - pfx]), dtype=np.int32)     # rows to compute per sequence
-        cu = np.zeros(lens.size + 1, dtype=np.int32)
-        np.cumsum(lens, out=cu[1:])
+        lens, cu = _lens_cu(np.concatenate([blens, full - pfx]))                             # rows to compute per sequence
         host = np.concatenate([cu, np.zeros(B, dtype=np.int32), pfx.astype(np.int32)])
         dev = torch.from_numpy(host).pin_memory().to(self.device, non_blocking=True)
         cu_dev, pfx_dev = dev[:lens.size + 1], dev[lens.size + 1:]
@@ -659,11 +643,7 @@ class LeafCLIPText:
                 verify_single_edit(ct, full, pfx, bt, blens, rho)
         t = torch.cat([bt, ct], 0)
         base_rows = int(cu[B])
-        need = base_rows * 3 * self.cfg.width * 2 * self.cfg.layers
-        if getattr(self, "_kv", None) is None or self._kv.numel() < need:
-            self._kv = None
-            with torch.cuda.device(self.device):
-                self._kv = torch.empty(max(need, 1), dtype=torch.uint8, device=self.device)
+        kvbuf = self._kv_buffer(0, base_rows)              # slot 0: the one encode_text_kv fills by default
         anchor = anchor.to(device=self.device, dtype=torch.float32).contiguous()
         idx = torch.empty(B, dtype=torch.int32, device=self.device)
         feat = torch.empty(B, self.cfg.embed_dim, dtype=torch.float32, device=self.device) if want_features else None
@@ -672,14 +652,14 @@ class LeafCLIPText:
         max_len = int(max(int(full.max()), int(blens.max())))
         rc = self._single_edit_call(single_edit, lambda: self._lib.leaf_score_candidates_prefix_fused(
             self._h, _ptr(self.flat), _ptr(self.w16), _ptr(t), C.c_void_p(lens.ctypes.data), _ptr(cu_dev), _ptr(pfx_dev), max_len,
-            _ptr(anchor), B, rho, _OBJ[objective], _ptr(idx), _ptr(feat), _ptr(loss), _ptr(self._kv), self._kv.numel(),
+            _ptr(anchor), B, rho, _OBJ[objective], _ptr(idx), _ptr(feat), _ptr(loss), _ptr(kvbuf), kvbuf.numel(),
             _ptr(ws), ws.numel(), self._stream()))
         if rc == 2:
             return None
         _lib.check(rc, "leaf_score_candidates_prefix_fused")
         self.rows_scored += int(cu[-1])
         # q0: without single_edit the fused launch keeps the captions' Q rows on chip, layer 0 of the cache holds K and V only
-        cache = {"kv": self._kv, "base_cu": cu_dev[:B + 1], "base_rows": base_rows, "lens": blens, "n": B, "arith": self.arithmetic_tag(),
+        cache = {"kv": kvbuf, "base_cu": cu_dev[:B + 1], "base_rows": base_rows, "lens": blens, "n": B, "arith": self.arithmetic_tag(),
                  "q0": bool(single_edit), "tokens": bt}
         return (idx, feat, cache, loss) if want_loss else (idx, feat, cache)
 
@@ -718,11 +698,7 @@ class LeafCLIPText:
         lens_p, cu, keep = self._train_plan
         t = self._tokens(text)
         n = t.shape[0]
-        need = self._lib.leaf_text_stash_bytes(self._h, n)
-        if self._stash is None or self._stash.numel() < need:
-            self._stash = None
-            with torch.cuda.device(self.device):
-                self._stash = torch.empty(need, dtype=torch.uint8, device=self.device)
+        stash = self._grow("stash", self._lib.leaf_text_stash_bytes(self._h, n))
         out = torch.empty(n, self.cfg.embed_dim, dtype=torch.float32, device=self.device)
         ws = self._workspace(2, n)
         if delta is not None:
@@ -730,8 +706,8 @@ class LeafCLIPText:
             if delta.dtype != torch.float32 or not delta.is_contiguous() or delta.numel() != rows * self.cfg.width:
                 raise ValueError(f"delta must be contiguous fp32 with {rows} x {self.cfg.width} elements")
         _lib.check(self._lib.leaf_text_forward_train_delta(self._h, _ptr(self.flat), _ptr(self.w16), _ptr(t), lens_p,
-                                                           _ptr(cu), n, _ptr(delta), _ptr(out), _ptr(self._stash),
-                                                           self._stash.numel(), _ptr(ws), ws.numel(), self._stream()),
+                                                           _ptr(cu), n, _ptr(delta), _ptr(out), _ptr(stash),
+                                                           stash.numel(), _ptr(ws), ws.numel(), self._stream()),
                    "leaf_text_forward_train_delta")
         self._train_tokens = t
         return out
@@ -750,7 +726,7 @@ class LeafCLIPText:
         ws = self._workspace(2, n)
         _lib.check(self._lib.leaf_textfare_input_grad(self._h, _ptr(self.flat), _ptr(self.w16_bwd), _ptr(t), lens_p,
                                                       _ptr(cu), n, _ptr(feat.contiguous()), _ptr(anchor),
-                                                      _ptr(self._stash), _ptr(g), _ptr(loss), _ptr(ws), ws.numel(),
+                                                      _ptr(self._buf["stash"]), _ptr(g), _ptr(loss), _ptr(ws), ws.numel(),
                                                       self._stream()), "leaf_textfare_input_grad")
         return loss, g
 
@@ -781,12 +757,12 @@ class LeafCLIPText:
             evs = (C.c_void_p * len(layer_events))(*[C.c_void_p(e.cuda_event) for e in layer_events])
             _lib.check(self._lib.leaf_textfare_backward_events(self._h, _ptr(self.flat), _ptr(self.w16_bwd), _ptr(t), lens_p,
                                                                _ptr(cu), n, _ptr(feat.contiguous()), _ptr(anchor), float(accum_scale),
-                                                               _ptr(self._stash), _ptr(self.grads), _ptr(loss), _ptr(ws),
+                                                               _ptr(self._buf["stash"]), _ptr(self.grads), _ptr(loss), _ptr(ws),
                                                                ws.numel(), self._stream(), evs), "leaf_textfare_backward_events")
             return loss
         _lib.check(self._lib.leaf_textfare_backward(self._h, _ptr(self.flat), _ptr(self.w16_bwd), _ptr(t), lens_p,
                                                     _ptr(cu), n, _ptr(feat.contiguous()), _ptr(anchor), float(accum_scale),
-                                                    _ptr(self._stash), _ptr(self.grads), _ptr(loss), _ptr(ws),
+                                                    _ptr(self._buf["stash"]), _ptr(self.grads), _ptr(loss), _ptr(ws),
                                                     ws.numel(), self._stream()), "leaf_textfare_backward")
         return loss
 

@@ -27,10 +27,10 @@ base = base.to(dev)
 anchor = model.encode_text(base, seq_lens=base_lens)
 sc = S.StepConfig(rho=rho, k_adv=1)
 T = {}
-orig = model._score_prefix
-def timed_prefix(*a, **k):
-    t0 = time.perf_counter(); r = orig(*a, **k); T.setdefault("score_prefix (plan + launch)", []).append(time.perf_counter() - t0); return r
-model._score_prefix = timed_prefix
+orig = model.score_candidates_run
+def timed_run(*a, **k):
+    t0 = time.perf_counter(); r = orig(*a, **k); T.setdefault("score_candidates_run (row plan + launch)", []).append(time.perf_counter() - t0); return r
+model.score_candidates_run = timed_run
 orig_pos = S.SyntheticCandidates.stage2_positions
 def timed_pos(self, pos, b1):
     t0 = time.perf_counter(); r = orig_pos(self, pos, b1); T.setdefault("stage2_positions", []).append(time.perf_counter() - t0); return r
@@ -42,8 +42,8 @@ for it in range(12):
     T.setdefault("search total", []).append(time.perf_counter() - t0)
 for k, v in T.items():
     v = np.array(v[2 * (len(v) // 12):]) * 1e6
-    print(f"{k:32s} median {np.median(v):8.1f} us  min {v.min():8.1f}")
-# breakdown of _score_prefix
+    print(f"{k:40s} median {np.median(v):8.1f} us  min {v.min():8.1f}")
+# breakdown of the search (score_candidates_run among it)
 import cProfile, pstats
 pr = cProfile.Profile(); pr.enable()
 for it in range(5): S.search_synthetic(model, anchor, base, sc, it, base_lens=base_lens)
