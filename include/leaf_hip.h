@@ -48,7 +48,7 @@ int leaf_text_set_chunk(leaf_text_t h, int seqs_per_chunk); /* sequences process
 /* options: "chunk" (as above), "last_layer_trim" (0/1, default 1: the last block's attention output, out-projection and
  * MLP are computed for the pooled EOT row only -- exact, every op after attention is row-wise), "compact_resid" (0/1, default 1:
  * the residual stream of the LN-folded forward-only passes as the 16-bit copy + a remainder byte per element instead of an fp32
- * row beside that copy -- see leaf_op_gemm_resid_ln8 below; 0, or LEAF_COMPACT_RESID=0, keeps fp32 rows), "single_edit" (0/1, default 0: see "single-edit passes" below), and the A/B switches "streams", "ln_fold", "fuse_attn", "normalize_fare" */
+ * row beside that copy -- see leaf_op_gemm_resid_ln8 below; 0, or LEAF_COMPACT_RESID=0, keeps fp32 rows), "single_edit" (0/1, default 0: see "single-edit passes" below), and the A/B switches "ln_fold", "fuse_attn", "normalize_fare" */
 int leaf_text_set_option(leaf_text_t h, const char* name, int value);
 /* current value of an option of leaf_text_set_option (+ "split_blocks"); -1 = unknown name */
 int leaf_text_get_option(leaf_text_t h, const char* name);
@@ -358,7 +358,7 @@ int leaf_tok_duplicate_map(const int32_t* tokens, int B, int rho, int ctx, int32
 
 /* ---- per-launch GEMM timing (bench.py roofline): between begin/end every GEMM launch is bracketed by HIP events on
  * its stream; end() sums duration / algorithmic FLOPs / algorithmic bytes / launches per key = kernel_family*16 + operand_dtype*8 + epilogue id
- * (family 0 = gemm_nt_kernel, 1 = gemm_nt256_kernel, 4 = gemm_nt256_half_kernel, 6 = gemm_nt64_ring_kernel; keys < 128). */
+ * (family 0 = gemm_nt_kernel, 4 = gemm_nt256_half_kernel, 6 = gemm_nt64_ring_kernel; keys < 128). */
 int leaf_prof_begin(void);
 int leaf_prof_pause(int paused);   /* suspend / resume the recording (per-launch events on a sample of the timed steps only) */
 int leaf_prof_end(double* ms, double* flops, double* bytes /* algorithmic, may be NULL */, int64_t* count, int n_keys);

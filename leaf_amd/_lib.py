@@ -160,6 +160,7 @@ DIAG_SIGS = {
     "leaf_debug_qkv_attn_plan": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "leaf_debug_gemm_stamps": (C.c_int, [C.c_void_p]),
     "leaf_debug_gemm_min_tiles": (C.c_int, [C.c_int]),
+    "leaf_debug_gemm_family": (C.c_int, [C.c_int] * 8),
 }
 VARIANTS_LIB = os.path.join(os.path.dirname(_HERE), "tools", "diag", "libleaf_hip_variants.so")
 _lib = None
@@ -194,8 +195,8 @@ def _bind(l, sigs, optional=False):
 
 
 def diag_lib():
-    """The diagnostic build with the kept experiments and the leaf_debug_* exports (make -C leaf_amd/csrc variants), loaded beside
-    the product library: host-side hooks only (the tile-plan test); GPU tools select it for the whole process with LEAF_HIP_LIB."""
+    """The diagnostic build with the leaf_debug_* exports (make -C leaf_amd/csrc variants), loaded beside
+    the product library: host-side hooks only (the tile-plan and GEMM-dispatch tests); GPU tools select it for the whole process with LEAF_HIP_LIB."""
     if not os.path.exists(VARIANTS_LIB):
         raise LeafHipError(f"{VARIANTS_LIB} not found: make -C leaf_amd/csrc variants (or __graft_entry__.build())")
     l = C.CDLL(VARIANTS_LIB)

@@ -27,7 +27,6 @@ extern "C" int leaf_version(void) { return 1; }
 // ------------------------------------------------------------------ options (include/leaf_hip.h leaf_text_set_option)
 namespace {
 int norm_flag(const leaf_text*, int v) { return v ? 1 : 0; }
-int norm_streams(const leaf_text*, int v) { return v >= 2 ? 2 : 1; }
 int norm_ln_fold(const leaf_text* h, int v) { return (v && h->cfg.width % 64 == 0) ? 1 : 0; }
 struct Option {
     const char* name;
@@ -38,7 +37,6 @@ struct Option {
 const Option OPTIONS[] = {
     {"chunk", &leaf_text::chunk, nullptr, nullptr},                 // set: leaf_text_set_chunk
     {"last_layer_trim", &leaf_text::last_trim, "LEAF_LAST_TRIM", norm_flag},
-    {"streams", &leaf_text::streams, nullptr, norm_streams},
     {"normalize_fare", &leaf_text::normalize_fare, nullptr, norm_flag},
     {"ln_fold", &leaf_text::ln_fold, "LEAF_LN_FOLD", norm_ln_fold},
     {"fuse_attn", &leaf_text::fuse_attn, "LEAF_FUSE_ATTN", norm_flag},
@@ -67,7 +65,6 @@ extern "C" int leaf_text_create(const leaf_text_cfg* cfg, int fwd_dtype, leaf_te
     h->cfg = *cfg;
     h->fwd_dtype = fwd_dtype;
     h->chunk = 4096;
-    h->streams = 1;   // 2 measured no faster on MI355X: the option stays for A/B runs
     for (const Option& o : OPTIONS)      // on unless the environment says NAME=0
         if (o.env) { const char* e = getenv(o.env); h->*o.member = (e && e[0] == '0') ? 0 : 1; }
     {   // gradient path: fp16 + per-step power-of-two loss scale unless LEAF_GRAD_DTYPE=bf16
@@ -116,9 +113,6 @@ extern "C" int leaf_text_create(const leaf_text_cfg* cfg, int fwd_dtype, leaf_te
 
 extern "C" void leaf_text_destroy(leaf_text_t h) {
     if (!h) return;
-    if (h->side) (void)hipStreamDestroy(h->side);
-    if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
-    if (h->ev_join) (void)hipEventDestroy(h->ev_join);
     for (int i = 0; i < leaf_text::PLAN_RING; ++i) {
         if (h->plan_ev[i]) { (void)hipEventSynchronize(h->plan_ev[i]); (void)hipEventDestroy(h->plan_ev[i]); }
         if (h->plan_host[i]) (void)hipHostFree(h->plan_host[i]);
@@ -350,7 +344,7 @@ extern "C" int leaf_prof_end_shapes(double* ms, double* flops, double* bytes, in
 extern "C" size_t leaf_text_workspace_bytes(leaf_text_t h, int n_seq, int mode) {
     if (!h || n_seq < 1) return 0;
     const int cs = n_seq < h->chunk ? n_seq : h->chunk;
-    size_t b = (h->streams >= 2 ? 2 : 1) * (fwd_chunk_bytes(h, cs) + 256) + 256;   // one buffer set per stream
+    size_t b = fwd_chunk_bytes(h, cs) + 512;      // alignment slack of the buffer set and of the workspace base
     if (mode == 1) b += align_up((size_t)n_seq * h->cfg.embed_dim * 4, 256) + 256;
     if (mode == 2) return leaf_train_ws_bytes(h, n_seq);
     return b;
@@ -625,6 +619,11 @@ extern "C" int leaf_debug_qkv_attn_plan(const int32_t* lens, int ctx, int s0, in
 }
 extern "C" int leaf_debug_gemm_stamps(void* buf) { leaf_gemm_set_stamps(buf); return 0; }
 extern "C" int leaf_debug_gemm_min_tiles(int n) { leaf_gemm256h_set_min_tiles(n); return 0; }
+extern "C" int leaf_debug_gemm_family(int M, int N, int K, int lda, int ldb, int ldc, int epi, int a_wrap) {
+    GemmArgs g;
+    g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ldc = ldc; g.ldx16 = N; g.a_wrap = a_wrap;
+    return leaf_gemm_family(g, epi);
+}
 #endif
 extern "C" int leaf_op_attention_fwd(const void* qkv, void* out, int n_seq, int ctx, int heads, int width, int dtype,
                                      leaf_stream_t s) {

@@ -26,11 +26,6 @@ struct leaf_text {
     int grad_dtype;  // 16-bit type of the gradient path: LEAF_F16 (loss-scaled, default) or LEAF_BF16
     int normalize_fare = 0;   // --normalize_fare: the training forward returns F.normalize(features), the backward follows
     float* scaler = nullptr;  // gradient-scaler state (device, leaf_hip.h LEAF_SC_*) or null: no saturation check, no back-off
-    // Two-stream chunk pipeline of the forward-only passes (forward.hip forward_all): sequence chunks alternate between the
-    // caller's stream and a side stream owned by the handle, so one chunk's HBM-bound kernels (LN, attention, the
-    // residual epilogues) and grid tails overlap the other chunk's MFMA-bound K loops.  Measured: kernels of the two
-    // streams do run concurrently, but the search pass is no faster (57.4 vs 56.0 ms), so the default is streams = 1.
-    int streams;
     // QKV GEMM -> attention as one launch in the big forward-only passes (qkv_attn.hip); option 'fuse_attn' / LEAF_FUSE_ATTN=0
     // restores the two kernels around the [rows, 3d] buffer.  The M-tile plan of a pass (first sequence of every tile) is cut on
     // the host and travels through a small ring of pinned buffers (an event per slot guards its re-use).
@@ -44,8 +39,6 @@ struct leaf_text {
     hipEvent_t plan_ev[PLAN_RING] = {};
     size_t plan_cap = 0;      // ints per slot
     int plan_next = 0;
-    hipStream_t side = nullptr;
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     std::vector<TensorInfo> tensors;
     std::vector<LayerOff> layer;
     size_t tok_emb, pos_emb, text_proj, lnf_w, lnf_b;

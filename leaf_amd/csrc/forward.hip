@@ -330,17 +330,6 @@ struct FwdPass {
     }
 };
 
-// rows below which a pass is not split across the two streams (the halves would not fill the chip anyway)
-constexpr size_t SPLIT_MIN_ROWS = 16384;
-
-int ensure_side_stream(leaf_text* h) {
-    if (h->side) return 0;
-    LEAF_TRY(hipStreamCreateWithFlags(&h->side, hipStreamNonBlocking));
-    LEAF_TRY(hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming));
-    LEAF_TRY(hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming));
-    return 0;
-}
-
 // Fused QKV + attention for the big passes: cut the chunk's sequences [s0, s1) into M tiles of whole sequences on the host and send the
 // cut points to tile_seq behind the work already queued on `s` (a pinned ring slot; its event keeps a slot from being rewritten early)
 int plan_attn_tiles(leaf_text* h, const int32_t* lens, int s0, int s1, const PrefixPlan& pp, int max_len, int32_t* tile_seq, hipStream_t s,
@@ -392,21 +381,12 @@ int forward_all(leaf_text* h, const float* P, const void* W, const int32_t* toke
         if (pp.max_len > 0 && pp.max_len < max_len) { leaf_set_error("max_len %d below a suffix length %d", pp.max_len, max_len); return 1; }
         max_len = pp.max_len > 0 && pp.max_len <= ctx ? pp.max_len : ctx;
     }
-    const int nsets = (h->streams >= 2 && total >= SPLIT_MIN_ROWS && n_seq >= 2 && !pp.kv_self_rows) ? 2 : 1;
-    size_t nchunks = (total + budget - 1) / budget;
+    const size_t nchunks = (total + budget - 1) / budget;
     if (pp.kv_self_rows && nchunks > 1) { leaf_set_error("fused pass: the captions and their candidates must fit one chunk (%zu rows > %zu)", total, budget); return 2; }
-    if (nsets == 2) nchunks = (nchunks + 1) / 2 * 2;                 // an even number of near-equal chunks
     const size_t target = (total + nchunks - 1) / nchunks;           // <= budget
-    FwdBuf bufs[2];
-    bufs[0] = carve_fwd(h, c, (int)(budget / ctx));
-    if (nsets == 2) bufs[1] = carve_fwd(h, c, (int)(budget / ctx));
+    const FwdBuf buf = carve_fwd(h, c, (int)(budget / ctx));
     if (!c.ok()) { leaf_set_error("workspace too small: need %zu bytes, have %zu", c.off, c.cap); return 1; }
-    if (nsets == 2) {
-        if (ensure_side_stream(h)) return 1;
-        LEAF_TRY(hipEventRecord(h->ev_fork, s));
-        LEAF_TRY(hipStreamWaitEvent(h->side, h->ev_fork, 0));
-    }
-    int s0 = 0, ci = 0;
+    int s0 = 0;
     size_t row0 = 0;
     while (s0 < n_seq) {
         int s1 = s0;
@@ -425,22 +405,15 @@ int forward_all(leaf_text* h, const float* P, const void* W, const int32_t* toke
         kv.kv_copy = pp.kv_copy;
         kv.kv_self_rows = pp.kv_self_rows;
         if (s1 == s0) { leaf_set_error("a sequence does not fit the row budget"); return 1; }
-        const int set = nsets == 2 ? (ci & 1) : 0;
-        hipStream_t cs_ = set ? h->side : s;
         if (h->fuse_attn && h->ln_fold && leaf_qkv_attn_eligible(h->cfg.width, h->cfg.heads, ctx, h->cfg.width, max_len) &&
             rows / 256 * (size_t)h->cfg.heads >= 256 &&      // at least a chip's worth of (256-row tile, head) items
-            plan_attn_tiles(h, lens, s0, s1, pp, max_len, bufs[set].tile_seq, cs_, kv))
+            plan_attn_tiles(h, lens, s0, s1, pp, max_len, buf.tile_seq, s, kv))
             return 1;
         if (forward_chunk(h, P, (const uint16_t*)W, tokens, s1 - s0, (int)rows, map, out + (size_t)s0 * h->cfg.embed_dim, normalize,
-                          bufs[set], cs_, kv, max_len))
+                          buf, s, kv, max_len))
             return 1;
         s0 = s1;
         row0 += rows;
-        ++ci;
-    }
-    if (nsets == 2) {
-        LEAF_TRY(hipEventRecord(h->ev_join, h->side));
-        LEAF_TRY(hipStreamWaitEvent(s, h->ev_join, 0));
     }
     return 0;
 }

@@ -1,6 +1,8 @@
 // NT GEMM on MFMA for the text tower:  C[M,N] (+)= A[M,K] * B[N,K]^T, 16-bit operands, fp32 accumulate.
-// This file: the first (register-staged) kernel, the two-stage 256^2 kernel and the DISPATCH over all GEMM kernels
-// (leaf_launch_gemm at the end: gemm256h.hip for >= 128 tiles of 256^2, gemm64.hip for small launches, these otherwise).
+// This file: the register-staged kernel and the DISPATCH over the three GEMM kernels (leaf_gemm_family / leaf_launch_gemm at the
+// end): the half-stage ring of gemm256h.hip for launches of >= 128 tiles of 256^2, the 64 x 128 ring of gemm64.hip for smaller
+// ones, and the kernel below for what neither ring takes: K < 192 (the tiny test config) and operands of 4 GiB or more, which
+// the rings' 32-bit byte offsets cannot span.
 //
 // Both operands are K-contiguous (nn.Linear weight layout [N,K]; activations [rows,K]), which is the
 // natural fragment shape of v_mfma_f32_16x16x32_{f16,bf16}: lane l holds 8 consecutive k of row l&15.
@@ -139,146 +141,13 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_kernel(GemmArgs p) {
     }
 }
 
-// ---------------------------------------------------------------------------------------------------------
-// 256x256x64 tile, 8 waves (2 x 4, 128 x 64 each), operands streamed HBM/L2 -> LDS by LDS-DMA
-// (global_load_lds_dwordx4, no staging registers), two 64-KiB stages, ONE raw s_barrier per K-tile:
-//     wait own DMA of tile t | barrier | issue DMA of tile t+1 into the other stage | MFMAs on tile t
-// so the next tile's transfer has the whole 64-MFMA phase to land.  The LDS image is lane-linear per DMA
-// piece (8 rows x 128 B), the XOR swizzle is applied to the per-lane SOURCE chunk and again on the read.
-// Halves L2->LDS bytes per FLOP vs the 128^2 kernel (1/128 B/FLOP) and LDS bytes per MFMA (0.375 KiB).
-constexpr int BM2 = 256, BN2 = 256;
-constexpr int TILE2 = BM2 * BK * 2;   // 32 KiB per operand per stage
-constexpr int STAGE2 = 2 * TILE2;     // 64 KiB
-
-typedef __attribute__((address_space(3))) void lds_void_t;
-typedef __attribute__((address_space(1))) const void glb_void_t;
-
-// Diagnostic build only (-DLEAF_GEMM_STAMPS): wave 0 stores s_memtime at five points of every block into p.stamps
-// (a buffer nothing else reads).  The shipped library is built without it.
-#ifdef LEAF_GEMM_STAMPS
-#define STAMP(i)                                                                                          \
-    if (p.stamps && threadIdx.x == 0) {                                                                   \
-        unsigned long long t_;                                                                            \
-        asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory");                        \
-        ((unsigned long long*)p.stamps)[(size_t)blockIdx.x * 8 + (i)] = t_;                               \
-    }
-#else
-#define STAMP(i)
-#endif
-
-template <class TT, int EPI>
-__global__ __launch_bounds__(512, 2) void gemm_nt256_kernel(GemmArgs p) {
-    leaf_fp16_sat_mode();
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wm = wid >> 2, wn = wid & 3;
-    const int tiles_n = p.N / BN2;
-    const int logical = xcd_remap(blockIdx.x, gridDim.x);
-    const int m0 = (logical / tiles_n) * BM2, n0 = (logical % tiles_n) * BN2;
-
-    // ---- DMA sources: wave w moves pieces w*4 + j (8 rows x 128 B each) of the A and of the B tile
-    const int prow = lane >> 3;                       // row inside the piece
-    const int schunk = (lane & 7) ^ prow;             // source-side swizzle (piece base is a multiple of 8 rows)
-    const u16* __restrict__ A = (const u16*)p.A;
-    const u16* __restrict__ B = (const u16*)p.B;
-    auto arow = [&](int j) { int r = m0 + (wid * 4 + j) * 8 + prow; return r < p.M ? r : p.M - 1; };
-    const u16* a0 = A + (size_t)arow(0) * p.lda + schunk * 8;
-    const u16* a1 = A + (size_t)arow(1) * p.lda + schunk * 8;
-    const u16* a2 = A + (size_t)arow(2) * p.lda + schunk * 8;
-    const u16* a3 = A + (size_t)arow(3) * p.lda + schunk * 8;
-    const u16* b0 = B + (size_t)(n0 + wid * 32 + prow) * p.ldb + schunk * 8;
-    const size_t bstep = (size_t)8 * p.ldb;
-    const int piece = wid * 4096;                     // byte offset of this wave's first piece inside a tile
-#define DMA16(src, dst) __builtin_amdgcn_global_load_lds((glb_void_t*)(src), (lds_void_t*)(dst), 16, 0, 0)
-#define ISSUE_TILE(stage, k0)                                                        \
-    {                                                                                \
-        char* sa_ = smem + (stage) * STAGE2 + piece;                                  \
-        char* sb_ = sa_ + TILE2;                                                     \
-        DMA16(a0 + (k0), sa_);          DMA16(a1 + (k0), sa_ + 1024);                \
-        DMA16(a2 + (k0), sa_ + 2048);   DMA16(a3 + (k0), sa_ + 3072);                \
-        DMA16(b0 + (k0), sb_);          DMA16(b0 + bstep + (k0), sb_ + 1024);        \
-        DMA16(b0 + 2 * bstep + (k0), sb_ + 2048); DMA16(b0 + 3 * bstep + (k0), sb_ + 3072); \
-    }
-
-    f32x4 acc[8][4];
-#pragma unroll
-    for (int i = 0; i < 8; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-    const int frow = lane & 15, fkc = lane >> 4;
-    // fragment offsets: rows frow + 16 i keep (row & 7) = frow & 7 -> one swizzled base per k-step + i * 2048
-    const int fo0 = lds_off(frow, fkc), fo1 = lds_off(frow, 4 + fkc);
-    const int xbase = wm * 128 * 128, wbase = TILE2 + wn * 64 * 128;
-#define COMPUTE2(stage)                                                                        \
-    {                                                                                          \
-        const char* st_ = smem + (stage) * STAGE2;                                             \
-        _Pragma("unroll") for (int ks = 0; ks < 2; ++ks) {                                     \
-            const int fo_ = ks ? fo1 : fo0;                                                    \
-            typename TT::vec8 xa[8], wb[4];                                                    \
-            _Pragma("unroll") for (int j = 0; j < 4; ++j)                                      \
-                wb[j] = *(const typename TT::vec8*)(st_ + wbase + fo_ + j * 2048);             \
-            _Pragma("unroll") for (int i = 0; i < 8; ++i)                                      \
-                xa[i] = *(const typename TT::vec8*)(st_ + xbase + fo_ + i * 2048);             \
-            _Pragma("unroll") for (int i = 0; i < 8; ++i)                                      \
-                _Pragma("unroll") for (int j = 0; j < 4; ++j)                                  \
-                    acc[i][j] = TT::mfma(wb[j], xa[i], acc[i][j]);                             \
-        }                                                                                      \
-    }
-
-    const int nt = p.K / BK;
-    STAMP(0)
-    ISSUE_TILE(0, 0)
-    for (int t = 0; t < nt - 1; ++t) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        if (t == 0) { STAMP(1) }
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-        ISSUE_TILE((t + 1) & 1, (t + 1) * BK)
-        COMPUTE2(t & 1)
-    }
-    STAMP(2)
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-    COMPUTE2((nt - 1) & 1)
-#undef DMA16
-#undef ISSUE_TILE
-#undef COMPUTE2
-
-    STAMP(3)
-    {
-        const int nbase = n0 + wn * 64 + 4 * (lane >> 4);
-        float4 bias4[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) bias4[j] = p.bias ? *(const float4*)(p.bias + nbase + 16 * j) : float4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {   // two batches of 4 x 4 fragments: 16 loads in flight per lane
-            int mrow[4];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) mrow[i] = m0 + wm * 128 + (4 * h + i) * 16 + frow;
-            f32x4 (&sub)[4][4] = *reinterpret_cast<f32x4 (*)[4][4]>(&acc[4 * h]);
-            epilogue_block<TT, EPI, 4, 4>(p, mrow, nbase, bias4, sub);
-        }
-    }
-    STAMP(4)
-}
-
+// 128-row tiles unless they would leave CUs idle (fewer tiles than the chip has CUs): then 64-row tiles
 template <class TT>
 hipError_t launch_t(const GemmArgs& p, int epi, hipStream_t s) {
-    static int use256 = -1;
-    if (use256 < 0) { const char* e = getenv("LEAF_GEMM256"); use256 = (e && e[0] == '0') ? 0 : 1; }
-    const bool big = use256 && p.N % BN2 == 0 && (long)((p.M + BM2 - 1) / BM2) * (p.N / BN2) >= 128;
-    // 128-row tiles unless they would leave CUs idle (fewer tiles than the chip has CUs): then 64-row tiles.
-    // LEAF_GEMM_BM64=0 disables the 64-row variant (A/B runs).
-    static int bm64 = -1;
-    if (bm64 < 0) { const char* e = getenv("LEAF_GEMM_BM64"); bm64 = (e && e[0] == '0') ? 0 : 1; }
     const long t128 = (long)((p.M + BM - 1) / BM) * (p.N / BN);
-    const bool half_m = !big && bm64 && t128 < 256 && p.M > 64;
-    const int grid = big ? ((p.M + BM2 - 1) / BM2) * (p.N / BN2)
-                         : (half_m ? ((p.M + 63) / 64) * (p.N / BN) : (int)t128);
-    const size_t lds = big ? 2 * STAGE2 : (half_m ? 2 * (64 * BK * 2 + TILE_BYTES) : 4 * TILE_BYTES);
+    const bool half_m = t128 < 256 && p.M > 64;
+    const int grid = half_m ? ((p.M + 63) / 64) * (p.N / BN) : (int)t128;
+    const size_t lds = half_m ? 2 * (64 * BK * 2 + TILE_BYTES) : 4 * TILE_BYTES;
 #define LEAF_GEMM_CASE(E)                                                                    \
     case E: {                                                                                \
         static bool attr_done = false;                                                       \
@@ -287,12 +156,9 @@ hipError_t launch_t(const GemmArgs& p, int epi, hipStream_t s) {
                                 hipFuncAttributeMaxDynamicSharedMemorySize, 4 * TILE_BYTES); \
             (void)hipFuncSetAttribute((const void*)gemm_nt_kernel<TT, E, 2>,                 \
                                 hipFuncAttributeMaxDynamicSharedMemorySize, 4 * TILE_BYTES); \
-            (void)hipFuncSetAttribute((const void*)gemm_nt256_kernel<TT, E>,                 \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 2 * STAGE2);     \
             attr_done = true;                                                                \
         }                                                                                    \
-        if (big) hipLaunchKernelGGL((gemm_nt256_kernel<TT, E>), dim3(grid), dim3(512), lds, s, p); \
-        else if (half_m) hipLaunchKernelGGL((gemm_nt_kernel<TT, E, 2>), dim3(grid), dim3(256), lds, s, p); \
+        if (half_m) hipLaunchKernelGGL((gemm_nt_kernel<TT, E, 2>), dim3(grid), dim3(256), lds, s, p); \
         else hipLaunchKernelGGL((gemm_nt_kernel<TT, E, 4>), dim3(grid), dim3(256), lds, s, p); \
         break;                                                                               \
     }
@@ -314,24 +180,12 @@ hipError_t launch_t(const GemmArgs& p, int epi, hipStream_t s) {
 
 }  // namespace
 
-// small launches: the 64 x 128 LDS-DMA ring kernel (gemm64.hip) unless LEAF_GEMM64=0
-static bool use_gemm64(const GemmArgs& p) {
-    static int on = -1;
-    if (on < 0) { const char* e = getenv("LEAF_GEMM64"); on = (e && e[0] == '0') ? 0 : 1; }
-    return on && leaf_gemm64_eligible(p);
-}
-
-// which kernel leaf_launch_gemm will pick: 4 = half-stage ring (gemm256h.hip; every launch with >= 128 tiles of 256^2 it can
-// take), 1 = gemm_nt256_kernel (two-stage 256^2: the act'(pre) epilogue of the backward), 6 = 64 x 128 ring (gemm64.hip, small
-// launches), 0 = gemm_nt_kernel (register-staged; K < 192 and the tiny test config)
+// THE dispatch rule (kernels.h): 4 = half-stage ring where it is eligible (>= 128 tiles of 256^2), else 6 = 64 x 128 ring, else
+// 0 = gemm_nt_kernel above (K < 192, and operands the rings' 32-bit offsets cannot span)
 int leaf_gemm_family(const GemmArgs& p, int epi) {
-    static int use256h = -1;   // LEAF_GEMM256H=0: A/B and test switch (the two-stage kernel then takes the big launches)
-    if (use256h < 0) { const char* e = getenv("LEAF_GEMM256H"); use256h = (e && e[0] == '0') ? 0 : 1; }
-    if (use256h && p.M > 0 && p.lda % 8 == 0 && p.ldb % 8 == 0 && leaf_gemm256h_eligible(p, epi)) return 4;
-    static int use256 = -1;
-    if (use256 < 0) { const char* e = getenv("LEAF_GEMM256"); use256 = (e && e[0] == '0') ? 0 : 1; }
-    if (use256 && p.N % 256 == 0 && (long)((p.M + 255) / 256) * (p.N / 256) >= 128) return 1;
-    return use_gemm64(p) ? 6 : 0;
+    if (leaf_gemm256h_eligible(p, epi)) return 4;
+    if (leaf_gemm64_eligible(p)) return 6;
+    return 0;
 }
 
 static void* g_stamps = nullptr;
@@ -345,7 +199,9 @@ hipError_t leaf_launch_gemm(const GemmArgs& p_in, int dtype, int epi, hipStream_
         return hipErrorInvalidValue;
     const int fam = leaf_gemm_family(p, epi);
     if (p.a_wrap && fam != 4) return hipErrorInvalidValue;      // only the half-stage ring kernel re-reads A (the caller duplicates it otherwise)
-    if (fam == 4) return leaf_launch_gemm256h(p, dtype, epi, s);
-    if (fam == 6) return leaf_launch_gemm64(p, dtype, epi, s);
-    return dtype == LEAF_F16 ? launch_t<F16>(p, epi, s) : launch_t<BF16>(p, epi, s);
+    switch (fam) {
+        case 4: return leaf_launch_gemm256h(p, dtype, epi, s);
+        case 6: return leaf_launch_gemm64(p, dtype, epi, s);
+        default: return dtype == LEAF_F16 ? launch_t<F16>(p, epi, s) : launch_t<BF16>(p, epi, s);
+    }
 }

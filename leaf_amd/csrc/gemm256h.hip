@@ -640,7 +640,8 @@ bool leaf_gemm256h_eligible(const GemmArgs& p, int epi) {
     const bool fits8 = epi != EPI_RESID_LN8 || ((unsigned long long)p.M * p.ldx16 * 2ull < (1ull << 32) && (unsigned long long)p.M * p.ldc < (1ull << 32));
     // a_wrap: A is [M, 64 a_wrap], read K / (64 a_wrap) times (at most twice: one wrap per tile walk)
     const bool wrap_ok = p.a_wrap == 0 || (p.a_wrap > 0 && p.K == 2 * BK * p.a_wrap && p.lda >= BK * p.a_wrap);
-    return p.N % BN == 0 && tiles >= g_min_tiles && p.K % BK == 0 && p.K >= 4 * BK && p.ldc % 8 == 0 && fits32 && fits8 && wrap_ok;
+    return p.M > 0 && p.N % BN == 0 && tiles >= g_min_tiles && p.K % BK == 0 && p.K >= 4 * BK && p.lda % 8 == 0 && p.ldb % 8 == 0 &&
+           p.ldc % 8 == 0 && fits32 && fits8 && wrap_ok;
 }
 
 hipError_t leaf_launch_gemm256h(const GemmArgs& p, int dtype, int epi, hipStream_t s) {

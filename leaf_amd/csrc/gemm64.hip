@@ -27,8 +27,8 @@ __device__ __forceinline__ void wait_vm_lgkm0() {
     asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"i"(N) : "memory");
 }
 
-// NS = ring slots: NS - 1 stages are in flight ahead of the MFMAs (3 slots -> two workgroups per CU; 5-6 slots -> one
-// workgroup per CU with a DMA latency of 4-5 stage times hidden, the better choice when a CU holds about one tile)
+// NS = ring slots: NS - 1 stages are in flight ahead of the MFMAs.  The launcher instantiates NS = 3 only (two workgroups per
+// CU); a 5-6 slot ring measured no faster: these launches run at the chip's L2 -> LDS rate either way.
 template <class TT, int EPI, int MI, int NS>
 __global__ __launch_bounds__(256, 2) void gemm_nt64_ring_kernel(GemmArgs p) {
     leaf_fp16_sat_mode();
@@ -170,9 +170,9 @@ __global__ __launch_bounds__(256, 2) void gemm_nt64_ring_kernel(GemmArgs p) {
     }
 }
 
-template <class TT, int MI, int NS>
+template <class TT, int MI>
 hipError_t launch64(const GemmArgs& p, int epi, hipStream_t s) {
-    constexpr int BM = 32 * MI;
+    constexpr int BM = 32 * MI, NS = 3;
     constexpr int RING = NS * (BM * BK * 2 + B_BYTES);
     if (p.K < NS * BK) return hipErrorInvalidValue;
     const int grid = ((p.M + BM - 1) / BM) * (p.N / BN);
@@ -203,11 +203,8 @@ hipError_t launch64(const GemmArgs& p, int epi, hipStream_t s) {
     return hipGetLastError();
 }
 
-// tile height: minimise (most tiles on one CU) x (bytes per stage); LEAF_GEMM64_MI = 2 | 3 | 4 forces one (A/B runs)
+// tile height: minimise (most tiles on one CU) x (bytes per stage)
 int pick_mi(const GemmArgs& p) {
-    static int forced = -1;
-    if (forced < 0) { const char* e = getenv("LEAF_GEMM64_MI"); forced = e ? atoi(e) : 0; }
-    if (forced >= 2 && forced <= 4) return forced;
     static int ncu = 0;
     if (!ncu) {
         int dev = 0;
@@ -235,21 +232,10 @@ bool leaf_gemm64_eligible(const GemmArgs& p) {
 
 hipError_t leaf_launch_gemm64(const GemmArgs& p, int dtype, int epi, hipStream_t s) {
     const bool f = dtype == LEAF_F16;
-    // LEAF_GEMM64_DEEP=1: 5-6 slot ring (one workgroup per CU, 4-5 stages of DMA latency hidden).  Measured no faster
-    // than the 3-slot ring (3,234 x 768 x 3,072: 30 us either way, and the same for 64 / 96 / 128-row tiles): these
-    // launches move ~270 MB from L2 to LDS in 30 us = 9 TB/s, the chip's L2 -> LDS rate, so the default stays 3 slots.
-    static int deep_on = -1;
-    if (deep_on < 0) { const char* e = getenv("LEAF_GEMM64_DEEP"); deep_on = (e && e[0] == '1') ? 1 : 0; }
     const int mi = pick_mi(p);
-    const bool deep = deep_on && p.K >= 6 * BK;
-#define GO(MI_, NS_) return f ? launch64<F16, MI_, NS_>(p, epi, s) : launch64<BF16, MI_, NS_>(p, epi, s)
-    if (deep) {
-        if (mi == 2) GO(2, 6);      // 6 x 24 KiB = 144 KiB
-        if (mi == 3) GO(3, 5);      // 5 x 28 KiB = 140 KiB
-        GO(4, 5);                   // 5 x 32 KiB = 160 KiB
-    }
-    if (mi == 2) GO(2, 3);
-    if (mi == 3) GO(3, 3);
-    GO(4, 3);
+#define GO(MI_) return f ? launch64<F16, MI_>(p, epi, s) : launch64<BF16, MI_>(p, epi, s)
+    if (mi == 2) GO(2);
+    if (mi == 3) GO(3);
+    GO(4);
 #undef GO
 }

@@ -60,7 +60,13 @@ struct GemmArgs {
 
 hipError_t leaf_launch_gemm(const GemmArgs& p, int dtype, int epi, hipStream_t s);
 void leaf_gemm_set_stamps(void* p);
-int leaf_gemm_family(const GemmArgs& p, int epi);   // 0 = gemm_nt_kernel, 1 = gemm_nt256_kernel (gemm.hip), 4 = half-stage ring, 6 = gemm64
+// The kernel leaf_launch_gemm gives a launch, the one statement of the dispatch rule (ids as in LEAF_PROF_KEY):
+//   4  gemm_nt256_half_kernel (gemm256h.hip)  if leaf_gemm256h_eligible: >= 128 tiles of 256^2, K >= 256, ldc % 8 == 0
+//   6  gemm_nt64_ring_kernel (gemm64.hip)     else if leaf_gemm64_eligible: K >= 192
+//   0  gemm_nt_kernel (gemm.hip, register-staged) otherwise: K < 192, and operands of >= 4 GiB, which the rings' 32-bit
+//      byte offsets cannot span
+// It answers for any arguments; leaf_launch_gemm refuses a launch with ldc % 4 != 0 (and the other strides it checks) before it asks.
+int leaf_gemm_family(const GemmArgs& p, int epi);
 // 256 x 256 tile, 64-deep half-stage LDS-DMA ring with full-line pieces (gemm256h.hip): the kernel of every launch with >= 128 tiles
 bool leaf_gemm256h_eligible(const GemmArgs& p, int epi);
 void leaf_gemm256h_set_min_tiles(int n);

@@ -216,8 +216,7 @@ class LeafCLIPText:
             pass
 
     def set_option(self, name: str, value: int):
-        """Engine switches (leaf_text_set_option): 'chunk', 'last_layer_trim', 'streams' (1 | 2: two-stream
-        chunk pipeline of the forward-only passes), 'normalize_fare' (training forward / backward on normalised features),
+        """Engine switches (leaf_text_set_option): 'chunk', 'last_layer_trim', 'normalize_fare' (training forward / backward on normalised features),
         'compact_resid' (1 default: the residual stream of the forward-only passes as the 16-bit copy + an 8-bit remainder per
         element instead of fp32 rows; 0 = fp32 rows), 'single_edit' (set per pass by the ``single_edit=`` argument of the scoring calls)."""
         if name == "ln_fold" and not value and getattr(self, "split_masks", ()):

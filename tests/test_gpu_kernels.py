@@ -5,7 +5,7 @@ import numpy as np
 import pytest
 
 from oracle import text_oracle as O
-from tests.util import ptr, rel_l2, stream, to16
+from tests.util import launch_families, ptr, rel_l2, stream, to16
 
 pytestmark = pytest.mark.gpu
 DT = {"bf16": 0, "fp16": 1}
@@ -272,7 +272,7 @@ def test_project_rows(env, normalize, M, d, D):
 
 @pytest.mark.parametrize("N,K", [(768, 768), (768, 3072), (3072, 768)])
 def test_gemm_rows_do_not_depend_on_the_kernel(env, N, K):
-    """The tile-count dispatch picks the 256^2 LDS-DMA kernel for big launches and the 128^2 kernel for small ones.
+    """The tile-count dispatch picks the 256^2 half-stage ring kernel for big launches and the 64 x 128 ring kernel for small ones.
     Every kernel accumulates k in ascending 32-steps into one fp32 accumulator per element and applies the same epilogue
     arithmetic, so a row's result must be BIT-identical whichever kernel computed it: the exactness of the prefix reuse
     (cache rows from a small launch, candidate rows from a big one) and of chunked passes rests on this."""
@@ -302,6 +302,102 @@ def test_gemm_rows_do_not_depend_on_the_kernel(env, N, K):
 
     for epi, act in ((0, 0), (1, 0), (1, 1), (2, 0), (3, 0)):
         assert torch.equal(run(epi, M, act), run(epi, CH, act)), f"epilogue {epi} act {act}"
+
+
+def _gemm_problem(torch, dev, dtype, M, N, K):
+    """Operands of one shape (16-bit A and B, bias, the fp32 output's initial value)"""
+    rng = np.random.default_rng(M + N + K)
+    a16 = to16(rng.standard_normal((M, K), dtype=np.float32), dtype, dev)
+    b16 = to16(rng.standard_normal((N, K), dtype=np.float32) * 0.1, dtype, dev)
+    bias = torch.from_numpy(rng.standard_normal(N).astype(np.float32)).to(dev)
+    x0 = torch.from_numpy(rng.standard_normal((M, N)).astype(np.float32)).to(dev)
+    return a16, b16, bias, x0
+
+
+def _check_gemm_family(env, dtype, M, N, K, family):
+    """Epilogues 0 / 2 / 3 of one launch: the kernel family that ran it, and the result against the float64 product of the rounded
+    operands (rel-L2 <= 2e-3 for the 16-bit store -- half an ulp of either 16-bit type is at most 2^-9 = 1.95e-3 of the element --
+    and <= 1e-5 for the fp32 epilogues)."""
+    lib, torch, dev = env
+    from leaf_amd import _lib
+    a16, b16, bias, x0 = _gemm_problem(torch, dev, dtype, M, N, K)
+    ref = a16.double() @ b16.double().T         # once for the three epilogues
+    for epi in (0, 2, 3):
+        c = torch.zeros(M, N, dtype=a16.dtype, device=dev) if epi == 0 else x0.clone()
+        fams = launch_families(lambda: _lib.check(lib.leaf_op_gemm(DT[dtype], epi, ptr(a16), ptr(b16), ptr(c), ptr(bias) if epi != 3 else None,
+                                                                   None, M, N, K, 0, 1.0 if epi == 3 else 0.0, 0, stream()), "gemm"))
+        torch.cuda.synchronize()
+        assert fams == {(family, epi, N, K): 1}, (epi, fams)
+        want = ref + bias.double() if epi == 0 else x0.double() + ref + (bias.double() if epi == 2 else 0.0)
+        err = float((c.double() - want).norm() / want.norm())
+        assert err <= (2e-3 if epi == 0 else 1e-5), (epi, err)      # NaN fails too
+
+
+def _ring64_mi(torch, M, N):
+    """Tile height (16-row MFMA tiles per wave) of the 64 x 128 ring kernel for a launch, by the cost of pick_mi (gemm64.hip) on this
+    device: fewest (tiles on the fullest CU) x (rows + columns of a stage), the lowest height first.  A copy of that rule, not a
+    reading of the launch: the profiler key holds the family only, so the tile height of a case is INFERRED.  Change pick_mi and
+    this together."""
+    ncu = torch.cuda.get_device_properties(0).multi_processor_count
+    cost = {mi: -(-(-(-M // (32 * mi)) * (N // 128)) // ncu) * (32 * mi + 128) for mi in (2, 3, 4)}
+    return min(cost, key=lambda mi: (cost[mi], mi))
+
+
+@pytest.mark.parametrize("M,N,K,family,mi", [
+    (11085, 768, 256, 4, None),       # 44 x 3 = 132 tiles of 256^2, the shortest K the half-stage ring takes
+    (8300, 1024, 192, 6, None),       # 132 tiles of 256^2 but K = 192: the shortest K of the 3-slot ring
+    (3234, 768, 3072, 6, 3),          # the B-caption launches: 96-row, 128-row and 64-row tiles
+    (3234, 2304, 768, 6, 4),
+    (2500, 768, 768, 6, 2),
+    (3234, 3072, 768, 4, None),       # 13 x 12 = 156 tiles of 256^2: the B-caption c_fc launch is the half-stage ring's
+    (700, 2304, 768, 6, None),
+    (333, 256, 448, 6, None),         # ragged M, odd number of K stages
+])
+def test_ring_gemm_kernels_against_float64(env, M, N, K, family, mi):
+    """Both LDS-DMA ring kernels (gemm256h.hip, gemm64.hip) and all three tile heights of the small one, on the launches the
+    dispatch gives them (leaf_amd/csrc/kernels.h leaf_gemm_family).  The family is read from the launch; the tile height is what
+    pick_mi's rule gives this device for the shape (_ring64_mi), checked so that a device with another CU count fails here rather
+    than quietly running one height three times."""
+    if mi is not None:
+        assert _ring64_mi(env[1], M, N) == mi
+    _check_gemm_family(env, "fp16", M, N, K, family)
+
+
+@pytest.mark.parametrize("dtype", ["fp16", "bf16"])
+@pytest.mark.parametrize("M,N,K", [
+    (40, 128, 64),          # one K tile, masked rows; M <= 64 keeps the 128-row tile
+    (333, 256, 128),        # 64-row tiles, ragged M
+    (4200, 1024, 128),      # 264 tiles of 128^2: the 128-row tile over several rounds
+    (8300, 1024, 128),      # 132 tiles of 256^2 that no ring takes (K < 192)
+])
+def test_register_staged_gemm_kernel_against_float64(env, dtype, M, N, K):
+    """gemm_nt_kernel (gemm.hip), the kernel of K < 192: both tile heights, both operand types."""
+    _check_gemm_family(env, dtype, M, N, K, 0)
+
+
+def test_register_staged_gemm_rows_do_not_depend_on_the_tile_height(env):
+    """4,200 rows in one launch run on 128-row tiles (264 tiles of 128^2), the same rows in launches of 200 on 64-row tiles (16 tiles
+    of 128^2 would leave CUs idle): every output row must be equal bit for bit, as test_gemm_rows_do_not_depend_on_the_kernel states
+    it for the ring kernels.  The tiny config (K = 128) runs on this kernel, and its prefix reuse and chunked passes rest on it."""
+    lib, torch, dev = env
+    from leaf_amd import _lib
+    M, N, K, CH = 4200, 1024, 128, 200
+    a16, b16, bias, x0 = _gemm_problem(torch, dev, "fp16", M, N, K)
+
+    def run(epi, rows):
+        outs = []
+        for r0 in range(0, M, rows):
+            c = torch.zeros(rows, N, dtype=torch.float16, device=dev) if epi == 0 else x0[r0:r0 + rows].clone()
+            _lib.check(lib.leaf_op_gemm(1, epi, ptr(a16[r0:r0 + rows]), ptr(b16), ptr(c), ptr(bias), None, rows, N, K, 0, 0.0, 0, stream()), "gemm")
+            outs.append(c)
+        torch.cuda.synchronize()
+        return torch.cat(outs)
+
+    for epi in (0, 2):
+        whole, chunked = [], []
+        fams = launch_families(lambda: (whole.append(run(epi, M)), chunked.append(run(epi, CH))))
+        assert fams == {(0, epi, N, K): 1 + M // CH}, fams
+        assert torch.equal(whole[0], chunked[0]), f"epilogue {epi}"
 
 
 @pytest.mark.parametrize("Ka,N", [(768, 768), (1024, 1024)])

@@ -4,12 +4,11 @@ losses and features are bit-identical to the same calls without the option and t
 
 Reference op: nn.MultiheadAttention inside ResidualAttentionBlock (src/open_clip/transformer.py:225,239-252); the candidates are the
 single-token substitutions of SURVEY.md section 8d."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
 from oracle import text_oracle as O
+from tests.util import launch_families
 
 pytestmark = pytest.mark.gpu
 
@@ -103,9 +102,9 @@ def test_single_edit_is_bit_identical(torch_mod, monkeypatch, model, dtype, prec
     _eq(torch_mod, on[3:], full2, "second stage against full recomputation")
 
 
-def test_single_edit_two_stream_split(torch_mod):
-    """A second-stage pass above 16,384 rows with the two-stream chunk pipeline: the halves run on two streams, each with fresh
-    rows of its own, both reading layer 0 of the same cache."""
+def test_single_edit_pass_above_16384_rows(torch_mod):
+    """A large second-stage pass, above 16,384 suffix rows: its 1,600 sequences fit one row-budget chunk, and every GEMM of it is a
+    launch of more than 128 tiles of 256^2.  With the option and without it, the pass equals the full recomputation bit for bit."""
     m = _model("ViT-L-14-quickgelu", 4)
     B, rho = 32, 50
     base = O.synthetic_tokens(B, seed=33, min_len=30, max_len=60)
@@ -118,31 +117,12 @@ def test_single_edit_two_stream_split(torch_mod):
     flat = cand.reshape(-1, 77)
     full = m.score_candidates(flat, anchor, rho, "l2", want_loss=True, seq_lens=lens)
     res = {}
-    for streams in (1, 2):
-        m.set_option("streams", streams)
-        for se in (False, True):
-            res[streams, se] = [x.clone() for x in m.score_candidates(flat, anchor, rho, "l2", want_loss=True, seq_lens=lens,
-                                                                      prefix_lens=pos.reshape(-1), kv=kv, single_edit=se)]
-    m.set_option("streams", 1)
-    for key, r in res.items():
-        _eq(torch_mod, r, full, f"streams, single_edit = {key} against full recomputation")
-
-
-def _families(m, fn):
-    """(kernel family, epilogue, N, K) -> launches of one call (leaf_prof_end_shapes)"""
-    from leaf_amd import _lib
-    lib = _lib.lib()
-    lib.leaf_prof_begin()
-    fn()
-    ng = 64
-    ms, fl, by = (C.c_double * ng)(), (C.c_double * ng)(), (C.c_double * ng)()
-    rows, info, n = (C.c_int64 * ng)(), (C.c_int32 * (4 * ng))(), C.c_int(0)
-    _lib.check(lib.leaf_prof_end_shapes(ms, fl, by, rows, info, ng, C.byref(n)), "prof")
-    out = {}
-    for i in range(n.value):
-        key = ((info[4 * i] % 1024) // 32, info[4 * i] % 16, info[4 * i + 1], info[4 * i + 2])
-        out[key] = out.get(key, 0) + info[4 * i + 3]
-    return out
+    for se in (False, True):
+        res[se] = [x.clone() for x in m.score_candidates(flat, anchor, rho, "l2", want_loss=True, seq_lens=lens,
+                                                         prefix_lens=pos.reshape(-1), kv=kv, single_edit=se)]
+    _eq(torch_mod, res[True], res[False], "single_edit on / off")
+    for se, r in res.items():
+        _eq(torch_mod, r, full, f"single_edit = {se} against full recomputation")
 
 
 @pytest.mark.parametrize("precision", ["rowsafe", "fast"])
@@ -167,8 +147,8 @@ def test_single_edit_replaces_the_fused_launch_of_block_0(torch_mod, precision):
         return lambda: m.score_candidates_fused(base, bl, flat, anchor, rho, lens, pos.reshape(-1), single_edit=se)
 
     for stage in (stage1, stage2):
-        off = _families(m, stage(False))
-        on = _families(m, stage(True))
+        off = launch_families(stage(False))
+        on = launch_families(stage(True))
         fused = lambda f: sum(c for (fam, e, N, K), c in f.items() if fam == 8 and N == 3 * d)
         fused_k3 = lambda f: sum(c for (fam, e, N, K), c in f.items() if fam == 8 and N == 3 * d and K == 3 * d)
         assert fused(off) == L, off

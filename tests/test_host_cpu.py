@@ -348,6 +348,53 @@ def test_fused_qkv_attention_tile_plan_properties():
             assert not caps or caps[-1] - caps[0] < ncap
 
 
+def test_gemm_dispatch_table(monkeypatch):
+    """leaf_gemm_family (leaf_amd/csrc/gemm.hip), the one statement of which kernel a GEMM launch gets, through its diagnostic export:
+    the four GEMMs of a block of ViT-L / ViT-H / bigG at 3,234 rows (a B-caption launch) and 124,464 rows (a scoring pass) with the
+    forward, LN-folded, 16 + 8-bit and backward epilogues go to the half-stage ring (4) from 128 tiles of 256^2 on and to the
+    64 x 128 ring (6) below; K = 128 (the tiny config) goes to the register-staged kernel (0) whatever the output's row stride."""
+    from leaf_amd import _lib
+    monkeypatch.delenv("LEAF_GEMM256H_MIN_TILES", raising=False)
+    fam = _lib.diag_lib().leaf_debug_gemm_family
+    STORE, ACT, RESID, STORE32, ACTGRAD, FOLD, FOLD_ACT, RESID_LN, RESID_LN8 = range(9)      # kernels.h EPI_*
+
+    def block_gemms(d):
+        """(N, K, lda, a_wrap, epilogues)"""
+        return [
+            (3 * d, d, d, 0, (STORE, FOLD)),                        # QKV
+            (d, d, d, 0, (RESID, RESID_LN, RESID_LN8)),             # out-projection
+            (4 * d, d, d, 0, (ACT, FOLD_ACT)),                      # c_fc
+            (d, 4 * d, 4 * d, 0, (RESID, RESID_LN, RESID_LN8)),     # c_proj
+            (3 * d, 3 * d, 3 * d, 0, (FOLD,)),                      # split block: [hi | lo | hi] x [hi | hi | lo]
+            (4 * d, 3 * d, 3 * d, 0, (FOLD_ACT,)),
+            (d, 2 * d, d, d // 64, (RESID, RESID_LN8)),             # split out-projection: A stored once, read twice
+            (d, 2 * d, 2 * d, 0, (RESID, RESID_LN8)),               # ... and on the duplicated panel
+            (4 * d, d, d, 0, (ACTGRAD,)),                           # backward: d c_proj, d c_fc, d out-projection, d QKV
+            (d, 4 * d, 4 * d, 0, (STORE32,)),
+            (d, d, d, 0, (STORE,)),
+            (d, 3 * d, 3 * d, 0, (STORE32,)),
+        ]
+
+    n = 0
+    for d in (768, 1024, 1280):
+        for M in (3234, 124464):
+            for N, K, lda, wrap, epis in block_gemms(d):
+                want = 4 if -(-M // 256) * (N // 256) >= 128 else 6
+                for epi in epis:
+                    assert fam(M, N, K, lda, K, N, epi, wrap) == want, (M, N, K, epi, wrap)
+                    # output rows of 4 but not 8 elements: only the 64 x 128 ring stores them.  (leaf_launch_gemm refuses
+                    # ldc % 4 != 0 before it asks for a family, so there is no such launch to pin one for.)
+                    assert fam(M, N, K, lda, K, N + 4, epi, wrap) == 6, (M, N, K, epi, wrap)
+                    n += 1
+    assert n == 3 * 2 * 20
+    d = 128                                                          # tiny config: K = d = 128 < 192
+    for M in (40, 3234, 124464):
+        for N in (3 * d, d, 4 * d):
+            for epi in (STORE, ACT, RESID, STORE32, ACTGRAD, FOLD, FOLD_ACT, RESID_LN, RESID_LN8):
+                for ldc in (N, N + 4):
+                    assert fam(M, N, d, d, d, ldc, epi, 0) == 0, (M, N, epi, ldc)
+
+
 def test_native_tokenizer_survives_fork():
     """the persistent worker pool of host_text.cpp is per process -- a forked child (a DataLoader worker, multiprocessing)
     inherits the pool object but none of its threads and used to wait for them for ever; now its first parallel call builds a

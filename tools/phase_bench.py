@@ -19,7 +19,6 @@ def main():
     ap.add_argument("--rho", type=int, default=50)
     ap.add_argument("--k-adv", type=int, default=1)
     ap.add_argument("--iters", type=int, default=5)
-    ap.add_argument("--streams", type=int, default=1)
     ap.add_argument("--chunk", type=int, default=0, help="sequences per pass (row budget = chunk * 77); 0 = engine default")
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
@@ -27,7 +26,6 @@ def main():
     model = create_model(a.model, device=dev, dtype="fp16", seed=1, trainable=True)
     frozen = LeafCLIPText(cfg, device=dev, dtype="fp16").copy_from(model)
     frozen.pack(); model.pack()
-    model.set_option('streams', a.streams); frozen.set_option('streams', a.streams)
     if a.chunk:
         model.set_option('chunk', a.chunk)
     sc = StepConfig(rho=a.rho, k_adv=a.k_adv)
