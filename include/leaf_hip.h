@@ -411,6 +411,17 @@ int leaf_op_classify(const float* feat, const float* class_feat, const int32_t* 
                      int32_t* pred, float* logits, int32_t* best_idx, float* best_feat, leaf_stream_t s);
 int leaf_op_attention_fwd(const void* qkv, void* out, int n_seq, int ctx, int heads, int width, int dtype,
                           leaf_stream_t s);
+/* the same launcher in every row mode (leaf_amd/csrc/attention.hip; RowMap in common.h).  All pointers are device pointers; kv, cu,
+ * prefix, base_cu and eot_pos may each be NULL.  cu [n_seq + 1]: packed rows (NULL: dense, ctx rows per sequence); prefix [n_seq]
+ * with kv [cache rows, 3 width] and base_cu [captions + 1]: positions < prefix[s] are read from the cache rows of caption
+ * (s - group_off) / group, and only positions >= prefix[s] are computed and written; eot_pos [n_seq]: one query row per sequence,
+ * written to out[sequence]; max_len: longest sequence of the launch (0: ctx), sizes the LDS image; single_edit: qkv is a
+ * [n_seq, 3 width] table with the one fresh row of each sequence at position prefix[s], every other position (Q included) comes
+ * from the cache, and sequences in front of group_off are captions read from the cache alone (an error without kv / prefix /
+ * base_cu). */
+int leaf_op_attention_fwd_map(const void* qkv, const void* kv, void* out, const int32_t* cu, const int32_t* prefix,
+                              const int32_t* base_cu, const int32_t* eot_pos, int n_seq, int ctx, int group, int group_off,
+                              int max_len, int single_edit, int heads, int width, int dtype, leaf_stream_t s);
 int leaf_op_layernorm(const float* x, const float* g, const float* b, float eps, void* out16, int rows, int width,
                       int dtype, leaf_stream_t s);
 int leaf_op_attention_bwd(const void* qkv, int qkv_dtype, const void* dout_bf16, void* dqkv_bf16, int n_seq, int ctx,

@@ -630,6 +630,13 @@ extern "C" int leaf_op_attention_fwd(const void* qkv, void* out, int n_seq, int 
     return leaf_check(leaf_launch_attention_fwd(qkv, nullptr, out, n_seq, RowMap{nullptr, 0, 0, ctx, nullptr, nullptr, 1}, heads, width, dtype,
                                                 (hipStream_t)s), "attention_fwd");
 }
+// ... and in every row mode of the launcher (tests/test_gpu_attention_modes.py): no logic of its own, the launcher checks the arguments
+extern "C" int leaf_op_attention_fwd_map(const void* qkv, const void* kv, void* out, const int32_t* cu, const int32_t* prefix,
+                                         const int32_t* base_cu, const int32_t* eot_pos, int n_seq, int ctx, int group, int group_off,
+                                         int max_len, int single_edit, int heads, int width, int dtype, leaf_stream_t s) {
+    return leaf_check(leaf_launch_attention_fwd(qkv, kv, out, n_seq, RowMap{cu, 0, 0, ctx, prefix, base_cu, group > 0 ? group : 1, group_off},
+                                                heads, width, dtype, (hipStream_t)s, eot_pos, max_len, single_edit), "attention_fwd_map");
+}
 extern "C" int leaf_op_layernorm(const float* x, const float* g, const float* b, float eps, void* out16, int rows,
                                  int width, int dtype, leaf_stream_t s) {
     return leaf_check(leaf_launch_layernorm(x, g, b, eps, out16, rows, width, dtype, (hipStream_t)s), "layernorm");

@@ -85,3 +85,73 @@ def trained_like_weights(cfg, seed=0, alpha=0.7, gain_sigma=0.5):
             scale = np.exp(0.4 * rng.standard_normal((v.shape[0], 1))).astype(np.float32)      # heavy-tailed token norms
             w[k] = (v * scale).astype(np.float32)
     return w
+
+
+# ---------------------------------------------------------------- float64 reference of the attention kernels' row modes
+# (leaf_amd/csrc/attention.hip, qkv_attn.hip; the operation: nn.MultiheadAttention in ResidualAttentionBlock).  Plain numpy, no code
+# shared with leaf_amd/: tests/test_gpu_attention_modes.py holds the kernels to it, tests/test_attention_ref_cpu.py pins it.
+def round16(x, dtype):
+    """float -> the nearest value of the 16-bit operand type ('fp16' | 'bf16'), as float64"""
+    from oracle import text_oracle as O
+    return (O.round_fp16(x) if dtype == "fp16" else O.round_bf16(x)).astype(np.float64)
+
+
+def attn_assemble(own, cache, lens, prefix=None, base_cu=None, group=1, group_off=0, edit=False):
+    """The full [prefix + len, 3d] q|k|v rows of every sequence (the `rowptr` rule of attention.hip, restated).
+    Sequence s computes lens[s] positions behind its first prefix[s] ones; s >= group_off belongs to caption (s - group_off) // group,
+    whose rows start at cache[base_cu[caption]].  Row modes: positions < prefix[s] are the caption's cache rows, the others the
+    sequence's own rows (own = the sequences' rows back to back).  Single-edit mode: own is a [n_seq, 3d] table with ONE row per
+    sequence, its position prefix[s]; every other position is the caption's cache row, and a sequence in front of group_off is
+    caption s itself, cache rows only."""
+    seqs, r = [], 0
+    for s, L in enumerate(lens):
+        L = int(L)
+        p = int(prefix[s]) if prefix is not None else 0
+        if edit:
+            cap = s if s < group_off else (s - group_off) // group
+            full = np.array(cache[base_cu[cap]: base_cu[cap] + p + L], np.float64)
+            if s >= group_off:
+                full[p] = own[s]
+        else:
+            full = np.array(own[r: r + L], np.float64)
+            if p:
+                cap = (s - group_off) // group
+                full = np.concatenate([np.asarray(cache[base_cu[cap]: base_cu[cap] + p], np.float64), full])
+        assert full.shape[0] == p + L
+        seqs.append(full)
+        r += L
+    return seqs
+
+
+def attn_seq_ref(seq, heads, model=None):
+    """softmax(q k^T / 8 + causal mask) v per head of one sequence's [T, 3d] q|k|v rows -> [T, d], float64.
+    model = 'fp16' | 'bf16': the rounding model of the kernels -- P rounded to the operand type before P V, the output rounded to it."""
+    seq = np.asarray(seq, np.float64)
+    T, d = seq.shape[0], heads * 64
+    q, k, v = (seq[:, i * d:(i + 1) * d].reshape(T, heads, 64).transpose(1, 0, 2) for i in range(3))
+    s = q @ k.transpose(0, 2, 1) / 8.0 + np.triu(np.full((T, T), -np.inf), 1)
+    p = np.exp(s - s.max(-1, keepdims=True))
+    p /= p.sum(-1, keepdims=True)
+    if model:
+        p = round16(p, model)
+    o = (p @ v).transpose(1, 0, 2).reshape(T, d)
+    return round16(o, model) if model else o
+
+
+def attn_slice(outs, prefix=None, eot=None):
+    """The rows a launch must write, in its output order: positions >= prefix[s] of every sequence, or its single eot[s] row."""
+    rows = []
+    for s, o in enumerate(outs):
+        if eot is not None:
+            rows.append(o[int(eot[s]): int(eot[s]) + 1])
+        else:
+            rows.append(o[(int(prefix[s]) if prefix is not None else 0):])
+    return np.concatenate(rows)
+
+
+def lnfold_rows_ref(x16, wp, s_vec, c_vec, mean, rstd, dtype):
+    """The q|k|v rows of the LN-folded projection (leaf_hip.h, leaf_op_gemm_lnfold): round16(rstd[m] (x16[m] . Wp[n] - mean[m] s[n]) +
+    c[n]) in float64"""
+    f = lambda a: np.asarray(a, np.float64)
+    acc = f(x16) @ f(wp).T
+    return round16(f(rstd)[:, None] * (acc - f(mean)[:, None] * f(s_vec)[None, :]) + f(c_vec)[None, :], dtype)
