@@ -210,6 +210,34 @@ int leaf_textfare_input_grad(leaf_text_t h, const float* params, const void* w16
                              const int32_t* seq_lens, const int32_t* cu_rows, int n_seq, const float* feat,
                              const float* anchor, const void* stash, float* d_embed, float* loss_out, void* ws,
                              size_t ws_bytes, leaf_stream_t s);
+/* ---- text embedding inversion (PEZ: src/pez/optim_utils.py:26-55,139-232; leaf_amd/inversion.py) ----
+ * The training forward for an INVERTED PROMPT [SOT, ids, EOT]: a projected id may itself be 49407 or 49406, so the pooled row is not
+ * "the first maximum token id" but the template's EOT slot (open_clip_pez/model.py:226 with the dummy ids of optim_utils.py:119-128),
+ * the LAST row of the sequence.  Same as leaf_text_forward_train except that it pools at row seq_lens[i] - 1 and keeps all
+ * seq_lens[i] rows whatever the ids are; seq_lens / cu_rows are REQUIRED, ws must hold n_seq x width floats. */
+int leaf_text_forward_train_last(leaf_text_t h, const float* params, const void* w16_fwd, const int32_t* tokens,
+                                 const int32_t* seq_lens, const int32_t* cu_rows, int n_seq, float* out, void* stash,
+                                 size_t stash_bytes, void* ws, size_t ws_bytes, leaf_stream_t s);
+/* Cosine head + input-gradient-only backward (optim_utils.py:191-196 with prompt_bs = batch_size = 1, for n_seq independent
+ * inversions at once): loss_b = loss_weight (1 - cos(feat_b, target_b)), the target normalised inside the head, fp32; d_embed (fp32
+ * [rows, width], un-scaled) = gradient of the SUM over b with respect to the token embeddings, so every sequence receives exactly
+ * the gradient of its own loss.  cos_out [n_seq] (device, may be NULL).  Option normalize_fare must be off. */
+int leaf_cosine_input_grad(leaf_text_t h, const float* params, const void* w16_bwd, const int32_t* tokens,
+                           const int32_t* seq_lens, const int32_t* cu_rows, int n_seq, const float* feat,
+                           const float* target, float loss_weight, const void* stash, float* d_embed,
+                           float* cos_out /* [n_seq] */, void* ws, size_t ws_bytes, leaf_stream_t s);
+/* Vocabulary projection (nn_project, optim_utils.py:26-55; leaf_amd/csrc/nnproj.hip): ids[m] = arg-max over v of
+ * (q[m] . table[v]) * inv_norm[v], cos[m] (may be NULL) = that value / ||q[m]||.  q [M, d], table [V, d], inv_norm [V] (from
+ * leaf_vocab_inv_norms: 1 / ||table[v]||, computed once while the weights are frozen), all fp32 on the device; any M >= 1, V >= 1,
+ * d % 4 == 0, d <= 2048 (an error otherwise); ws: leaf_nn_project_ws_bytes(M, V) bytes.  Exact fp32 products on the matrix cores,
+ * ONE summation order per (row, id): a row's ids / cos bits depend on neither M, its place in the launch nor the launch.  Order of
+ * the arg-max: NaN first, larger value, lower id (as leaf_select_topk) -- identical table rows resolve to the lower id, a NaN
+ * query row returns id 0.  The table is read from HBM once per call. */
+int leaf_vocab_inv_norms(const float* table, int V, int d, float* inv_norm, leaf_stream_t s);
+size_t leaf_nn_project_ws_bytes(int M, int V);
+int leaf_nn_project(const float* q, int M, const float* table, const float* inv_norm, int V, int d, int32_t* ids,
+                    float* cos /* may be NULL */, void* ws, size_t ws_bytes, leaf_stream_t s);
+
 /* fused grad-sign / normalise - step - project on the resident perturbation, per sequence over its kept rows:
  * norm 0 (linf): delta <- clamp(delta + alpha sign(grad), -eps, eps)       (utils_attacks.py:693-694)
  * norm 2 (l2)  : delta <- renorm_2(delta + alpha grad / ||grad||_2, eps)   (src/robust_vlm/train/utils.py:96-114)
@@ -409,6 +437,10 @@ int leaf_op_qkv_attn(int dtype, const void* x16, const void* Wp, const float* c_
 /* the classification score of leaf_score_candidates_cls alone, on given feature rows feat [B*rho, D] (kernel hook for the tests) */
 int leaf_op_classify(const float* feat, const float* class_feat, const int32_t* labels, int B, int rho, int D, int C, float* loss,
                      int32_t* pred, float* logits, int32_t* best_idx, float* best_feat, leaf_stream_t s);
+/* the cosine head of leaf_cosine_input_grad alone (kernel hook for the tests): dout [B, D] = d (sum_b loss_b) / d feat, cos_out [B]
+ * (may be NULL); ws: 64 + 2 B device floats */
+int leaf_op_cosine_head(const float* feat, const float* target, int B, int D, float loss_weight, float* dout, float* cos_out,
+                        float* ws, leaf_stream_t s);
 int leaf_op_attention_fwd(const void* qkv, void* out, int n_seq, int ctx, int heads, int width, int dtype,
                           leaf_stream_t s);
 /* the same launcher in every row mode (leaf_amd/csrc/attention.hip; RowMap in common.h).  All pointers are device pointers; kv, cu,

@@ -86,13 +86,17 @@ extern "C" size_t leaf_text_stash_bytes(leaf_text_t h, int n_seq) {
     return align_up(c.off, 256) + 256;
 }
 
-extern "C" int leaf_text_forward_train_delta(leaf_text_t h, const float* P, const void* w16_fwd, const int32_t* tokens,
-                                             const int32_t* seq_lens, const int32_t* cu_rows, int n_seq,
-                                             const float* delta, float* out, void* stash, size_t stash_bytes, void* ws,
-                                             size_t ws_bytes, leaf_stream_t s_) {
+// pool_last: pool at the last kept row of each sequence instead of the first maximum token id (leaf_text_forward_train_last)
+static int forward_train_impl(leaf_text_t h, const float* P, const void* w16_fwd, const int32_t* tokens, const int32_t* seq_lens,
+                              const int32_t* cu_rows, int n_seq, const float* delta, float* out, void* stash, size_t stash_bytes,
+                              void* ws, size_t ws_bytes, leaf_stream_t s_, bool pool_last) {
     if (!h || !P || !w16_fwd || !tokens || !out || !stash || n_seq < 1) { leaf_set_error("null/invalid argument"); return 1; }
     hipStream_t s = (hipStream_t)s_;
     if ((seq_lens == nullptr) != (cu_rows == nullptr)) { leaf_set_error("seq_lens (host) and cu_rows (device) go together"); return 1; }
+    if (pool_last && (!seq_lens || !ws || ws_bytes < (size_t)n_seq * h->cfg.width * 4)) {
+        leaf_set_error("forward_train_last needs explicit seq_lens / cu_rows and a workspace of n_seq x width floats");
+        return 1;
+    }
     const leaf_text_cfg& cf = h->cfg;
     const int rows = (int)total_rows(h, seq_lens, n_seq);
     Carver c(stash, stash_bytes);
@@ -129,16 +133,37 @@ extern "C" int leaf_text_forward_train_delta(leaf_text_t h, const float* P, cons
     if (leaf_project_rows_ok(d, cf.embed_dim) && ws && ws_bytes >= (size_t)n_seq * d * 4) {
         // pooled rows -> ws, ln_final -> st.pooled (the stash the backward reads), fp32 matrix-core projection -> out
         float* xg = (float*)ws;
-        LEAF_TRY(leaf_launch_eot_positions(tokens, st.eot, n_seq, map, s));
+        if (pool_last) LEAF_TRY(leaf_launch_last_positions(st.eot, n_seq, map, s));
+        else LEAF_TRY(leaf_launch_eot_positions(tokens, st.eot, n_seq, map, s));
         LEAF_TRY(leaf_launch_gather_rows(st.xin + (size_t)L * rd, st.eot, xg, n_seq, map, d, s));
         LEAF_TRY(leaf_launch_project_rows(xg, P + h->lnf_w, P + h->lnf_b, cf.ln_eps, P + h->text_proj, st.pooled, out, n_seq, d,
                                           cf.embed_dim, 0, s));
+    } else if (pool_last) {
+        // the same pooled rows through the generic projection kernel, which then reads one row per sequence and leaves st.eot alone
+        float* xg = (float*)ws;
+        LEAF_TRY(leaf_launch_last_positions(st.eot, n_seq, map, s));
+        LEAF_TRY(leaf_launch_gather_rows(st.xin + (size_t)L * rd, st.eot, xg, n_seq, map, d, s));
+        LEAF_TRY(leaf_launch_pool_project(xg, tokens, P + h->lnf_w, P + h->lnf_b, cf.ln_eps, P + h->text_proj, out, st.pooled,
+                                          nullptr, n_seq, map, d, cf.embed_dim, 0, s, 1));
     } else {
         LEAF_TRY(leaf_launch_pool_project(st.xin + (size_t)L * rd, tokens, P + h->lnf_w, P + h->lnf_b, cf.ln_eps,
                                           P + h->text_proj, out, st.pooled, st.eot, n_seq, map, d, cf.embed_dim, 0, s));
     }
     if (h->normalize_fare) LEAF_TRY(leaf_launch_normalize_rows(out, st.norms, n_seq, cf.embed_dim, s));   // utils_AT.py:319
     return 0;
+}
+
+extern "C" int leaf_text_forward_train_delta(leaf_text_t h, const float* P, const void* w16_fwd, const int32_t* tokens,
+                                             const int32_t* seq_lens, const int32_t* cu_rows, int n_seq,
+                                             const float* delta, float* out, void* stash, size_t stash_bytes, void* ws,
+                                             size_t ws_bytes, leaf_stream_t s_) {
+    return forward_train_impl(h, P, w16_fwd, tokens, seq_lens, cu_rows, n_seq, delta, out, stash, stash_bytes, ws, ws_bytes, s_, false);
+}
+
+extern "C" int leaf_text_forward_train_last(leaf_text_t h, const float* P, const void* w16_fwd, const int32_t* tokens,
+                                            const int32_t* seq_lens, const int32_t* cu_rows, int n_seq, float* out, void* stash,
+                                            size_t stash_bytes, void* ws, size_t ws_bytes, leaf_stream_t s_) {
+    return forward_train_impl(h, P, w16_fwd, tokens, seq_lens, cu_rows, n_seq, nullptr, out, stash, stash_bytes, ws, ws_bytes, s_, true);
 }
 
 extern "C" int leaf_text_forward_train(leaf_text_t h, const float* P, const void* w16_fwd, const int32_t* tokens,
@@ -148,13 +173,22 @@ extern "C" int leaf_text_forward_train(leaf_text_t h, const float* P, const void
                                          ws, ws_bytes, s_);
 }
 
+// The loss whose gradient the backward starts from: TextFARE against an anchor (ref = anchor, scale = accum_scale, out = the
+// loss, one float) or the cosine head of text embedding inversion (ref = target, scale = loss_weight, out = cos [n_seq]).
+struct LossHead {
+    bool cosine;
+    const float* ref;
+    float scale;
+    float* out;
+};
+
 // Shared body of the parameter-gradient backward (G != null) and of the input-gradient-only backward of the optional
 // embedding-space PGD mode (G == null, d_embed != null: no weight / bias / LayerNorm / embedding-table gradients).
 static int backward_impl(leaf_text_t h, const float* P, const void* w16_bwd, const int32_t* tokens,
                          const int32_t* seq_lens, const int32_t* cu_rows, int n_seq, const float* feat,
-                         const float* anchor, float accum_scale, const void* stash, float* G, float* d_embed,
-                         float* loss_out, void* ws, size_t ws_bytes, leaf_stream_t s_, void* const* layer_events = nullptr) {
-    if (!h || !P || !w16_bwd || !tokens || !feat || !anchor || !stash || (!G && !d_embed) || !ws || n_seq < 1) {
+                         const LossHead& head, const void* stash, float* G, float* d_embed, void* ws, size_t ws_bytes,
+                         leaf_stream_t s_, void* const* layer_events = nullptr) {
+    if (!h || !P || !w16_bwd || !tokens || !feat || !head.ref || !stash || (!G && !d_embed) || !ws || n_seq < 1) {
         leaf_set_error("null/invalid argument");
         return 1;
     }
@@ -175,8 +209,11 @@ static int backward_impl(leaf_text_t h, const float* P, const void* w16_bwd, con
     const float* inv_s = b.gscale + 1;
     const uint16_t* WT = (const uint16_t*)w16_bwd;
 
-    LEAF_TRY(leaf_launch_fare_loss(feat, anchor, n_seq, D, accum_scale, loss_out, b.dout, b.gscale, gk == 1, s,
-                                   h->normalize_fare ? st.norms : nullptr, h->scaler));
+    if (head.cosine)
+        LEAF_TRY(leaf_launch_cos_loss(feat, head.ref, n_seq, D, head.scale, head.out, b.dout, b.gscale, gk == 1, s));
+    else
+        LEAF_TRY(leaf_launch_fare_loss(feat, head.ref, n_seq, D, head.scale, head.out, b.dout, b.gscale, gk == 1, s,
+                                       h->normalize_fare ? st.norms : nullptr, h->scaler));
     const bool sat_check = h->scaler && G && gk == 1;     // fp16 gradient path with a scaler attached (leaf_hip.h "gradient scaler")
     LEAF_TRY(hipMemsetAsync(b.dx, 0, rd * 4, s));
     LEAF_TRY(leaf_launch_pool_project_bwd(b.dout, st.pooled, st.xin + (size_t)L * rd, st.eot, P + h->lnf_w, P + h->lnf_b,
@@ -263,8 +300,8 @@ extern "C" int leaf_textfare_backward(leaf_text_t h, const float* P, const void*
                                       const void* stash, float* G, float* loss_out, void* ws, size_t ws_bytes,
                                       leaf_stream_t s_) {
     if (!G) { leaf_set_error("null/invalid argument"); return 1; }
-    return backward_impl(h, P, w16_bwd, tokens, seq_lens, cu_rows, n_seq, feat, anchor, accum_scale, stash, G, nullptr,
-                         loss_out, ws, ws_bytes, s_);
+    return backward_impl(h, P, w16_bwd, tokens, seq_lens, cu_rows, n_seq, feat, LossHead{false, anchor, accum_scale, loss_out}, stash, G,
+                         nullptr, ws, ws_bytes, s_);
 }
 
 // The same backward with completion events for gradient-bucket overlap: layer_events[l], l = L-1 .. 0, is recorded
@@ -276,8 +313,8 @@ extern "C" int leaf_textfare_backward_events(leaf_text_t h, const float* P, cons
                                              float* loss_out, void* ws, size_t ws_bytes, leaf_stream_t s_,
                                              void* const* layer_events) {
     if (!G) { leaf_set_error("null/invalid argument"); return 1; }
-    return backward_impl(h, P, w16_bwd, tokens, seq_lens, cu_rows, n_seq, feat, anchor, accum_scale, stash, G, nullptr,
-                         loss_out, ws, ws_bytes, s_, layer_events);
+    return backward_impl(h, P, w16_bwd, tokens, seq_lens, cu_rows, n_seq, feat, LossHead{false, anchor, accum_scale, loss_out}, stash, G,
+                         nullptr, ws, ws_bytes, s_, layer_events);
 }
 
 extern "C" int leaf_textfare_input_grad(leaf_text_t h, const float* P, const void* w16_bwd, const int32_t* tokens,
@@ -285,8 +322,46 @@ extern "C" int leaf_textfare_input_grad(leaf_text_t h, const float* P, const voi
                                         const float* anchor, const void* stash, float* d_embed, float* loss_out, void* ws,
                                         size_t ws_bytes, leaf_stream_t s_) {
     if (!d_embed) { leaf_set_error("null/invalid argument"); return 1; }
-    return backward_impl(h, P, w16_bwd, tokens, seq_lens, cu_rows, n_seq, feat, anchor, 1.0f, stash, nullptr, d_embed,
-                         loss_out, ws, ws_bytes, s_);
+    return backward_impl(h, P, w16_bwd, tokens, seq_lens, cu_rows, n_seq, feat, LossHead{false, anchor, 1.0f, loss_out}, stash, nullptr,
+                         d_embed, ws, ws_bytes, s_);
+}
+
+extern "C" int leaf_cosine_input_grad(leaf_text_t h, const float* P, const void* w16_bwd, const int32_t* tokens,
+                                      const int32_t* seq_lens, const int32_t* cu_rows, int n_seq, const float* feat,
+                                      const float* target, float loss_weight, const void* stash, float* d_embed, float* cos_out,
+                                      void* ws, size_t ws_bytes, leaf_stream_t s_) {
+    if (!d_embed) { leaf_set_error("null/invalid argument"); return 1; }
+    if (h && h->normalize_fare) { leaf_set_error("cosine_input_grad: option normalize_fare must be off"); return 1; }
+    return backward_impl(h, P, w16_bwd, tokens, seq_lens, cu_rows, n_seq, feat, LossHead{true, target, loss_weight, cos_out}, stash,
+                         nullptr, d_embed, ws, ws_bytes, s_);
+}
+
+// the cosine head alone (kernel hook for the tests): dout [B, D], cos_out [B]; ws = 64 + 2 B floats
+extern "C" int leaf_op_cosine_head(const float* feat, const float* target, int B, int D, float loss_weight, float* dout,
+                                   float* cos_out, float* ws, leaf_stream_t s) {
+    if (!feat || !target || !dout || !ws || B < 1 || D < 1) { leaf_set_error("null/invalid argument"); return 1; }
+    return leaf_check(leaf_launch_cos_loss(feat, target, B, D, loss_weight, cos_out, dout, ws, 0, (hipStream_t)s), "cosine_head");
+}
+
+extern "C" int leaf_vocab_inv_norms(const float* table, int V, int d, float* inv_norm, leaf_stream_t s) {
+    if (!table || !inv_norm || V < 1) { leaf_set_error("vocab_inv_norms: null/invalid argument"); return 1; }
+    if (!leaf_nn_project_ok(d)) { leaf_set_error("vocab_inv_norms: d = %d must be a multiple of 4, at most 2048", d); return 1; }
+    return leaf_check(leaf_launch_vocab_inv_norms(table, V, d, inv_norm, (hipStream_t)s), "vocab_inv_norms");
+}
+
+// sized for the lowest slab (16 table rows) so that it does not depend on d
+extern "C" size_t leaf_nn_project_ws_bytes(int M, int V) {
+    if (M < 1 || V < 1) return 0;
+    return align_up((size_t)((V + 15) / 16) * (size_t)M * 8, 256);
+}
+
+extern "C" int leaf_nn_project(const float* q, int M, const float* table, const float* inv_norm, int V, int d, int32_t* ids,
+                               float* cos, void* ws, size_t ws_bytes, leaf_stream_t s) {
+    if (!q || !table || !inv_norm || !ids || !ws || M < 1 || V < 1) { leaf_set_error("nn_project: null/invalid argument"); return 1; }
+    if (!leaf_nn_project_ok(d)) { leaf_set_error("nn_project: d = %d must be a multiple of 4, at most 2048", d); return 1; }
+    const size_t need = (size_t)leaf_nn_project_slabs(V, d) * (size_t)M * 8;
+    if (ws_bytes < need) { leaf_set_error("nn_project: workspace too small: need %zu bytes, have %zu", need, ws_bytes); return 1; }
+    return leaf_check(leaf_launch_nn_project(q, M, table, inv_norm, V, d, ids, cos, ws, (hipStream_t)s), "nn_project");
 }
 
 extern "C" int leaf_pgd_step(float* delta, const float* grad, const int32_t* cu_rows, int n_seq, int ctx, int width,

@@ -402,6 +402,16 @@ __global__ __launch_bounds__(256) void eot_positions_kernel(const int32_t* __res
     if (lane == 0) eot_pos[n] = bi;
 }
 
+// the last kept position of each sequence: the pooling row of a prompt whose ids may hold EOT anywhere (the template's EOT slot,
+// src/pez/open_clip_pez/model.py:226 with the dummy ids of optim_utils.py:119-128)
+__global__ __launch_bounds__(256) void last_positions_kernel(int32_t* __restrict__ eot_pos, int n_seq, RowMap map) {
+    leaf_fp16_sat_mode();
+    const int n = blockIdx.x * 256 + threadIdx.x;
+    if (n >= n_seq) return;
+    const int sg = map.s0 + n;
+    eot_pos[n] = seq_prefix(map, sg) + seq_len(map, sg) - 1;
+}
+
 __global__ __launch_bounds__(256) void gather_rows_kernel(const float* __restrict__ x, const int32_t* __restrict__ eot_pos,
                                                           float* __restrict__ out, int n_seq, RowMap map, int d) {
     leaf_fp16_sat_mode();
@@ -551,6 +561,11 @@ hipError_t leaf_launch_pool_project(const float* x, const int32_t* tokens, const
 
 hipError_t leaf_launch_eot_positions(const int32_t* tokens, int32_t* eot_pos, int n_seq, RowMap map, hipStream_t s) {
     hipLaunchKernelGGL(eot_positions_kernel, dim3((n_seq + 3) / 4), dim3(256), 0, s, tokens, eot_pos, n_seq, map);
+    return hipGetLastError();
+}
+
+hipError_t leaf_launch_last_positions(int32_t* eot_pos, int n_seq, RowMap map, hipStream_t s) {
+    hipLaunchKernelGGL(last_positions_kernel, dim3((n_seq + 255) / 256), dim3(256), 0, s, eot_pos, n_seq, map);
     return hipGetLastError();
 }
 

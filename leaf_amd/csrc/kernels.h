@@ -164,6 +164,15 @@ hipError_t leaf_launch_attention_fwd(const void* qkv, const void* kv_base, void*
                                      int single_edit = 0);
 // eot_pos[n] = first index of the maximum token id among the kept positions (torch argmax pooling)
 hipError_t leaf_launch_eot_positions(const int32_t* tokens, int32_t* eot_pos, int n_seq, RowMap map, hipStream_t s);
+// eot_pos[n] = the last kept position of sequence n, whatever its tokens are (the pooling row of an inverted prompt, nnproj.hip)
+hipError_t leaf_launch_last_positions(int32_t* eot_pos, int n_seq, RowMap map, hipStream_t s);
+// vocabulary projection (nnproj.hip): inverse row norms of the table, and ids / cos of the cosine-nearest table row per query row;
+// ws: leaf_nn_project_slabs(V, d) * M * 8 bytes
+bool leaf_nn_project_ok(int d);
+int leaf_nn_project_slabs(int V, int d);
+hipError_t leaf_launch_vocab_inv_norms(const float* table, int V, int d, float* inv_norm, hipStream_t s);
+hipError_t leaf_launch_nn_project(const float* q, int M, const float* table, const float* inv_norm, int V, int d, int32_t* ids,
+                                  float* cosv, void* ws, hipStream_t s);
 // out[n,:] = x[row of position eot_pos[n] of sequence n,:]   (fp32)
 hipError_t leaf_launch_gather_rows(const float* x, const int32_t* eot_pos, float* out, int n_seq, RowMap map, int d,
                                    hipStream_t s);
@@ -185,6 +194,10 @@ hipError_t leaf_launch_fare_loss(const float* feat, const float* anchor, int B, 
                                  float* dout, float* gscale, int use_scaling, hipStream_t s,
                                  const float* norms = nullptr /* --normalize_fare: ||f|| per caption, feat is f / ||f|| */,
                                  const float* scaler = nullptr /* gradient-scaler state (leaf_hip.h): S *= 2^scaler[LEAF_SC_BACKOFF] */);
+// cosine head of text embedding inversion (PEZ, src/pez/optim_utils.py:191-196) with the outputs and loss-scale protocol of
+// leaf_launch_fare_loss: loss_b = weight (1 - cos(feat_b, target_b)), dout = d (sum_b loss_b) / d feat, cos_out[b] (may be null)
+hipError_t leaf_launch_cos_loss(const float* feat, const float* target, int B, int D, float weight, float* cos_out,
+                                float* dout, float* gscale, int use_scaling, hipStream_t s);
 // fp16 gradient path: raise scaler[LEAF_SC_SAT_FLAG] and poison *poison (gradient element 0) with NaN when any of the n <= 5
 // 16-bit tensors holds a saturated (|x| >= 65504) or non-finite value; numel multiples of 8, pointers 16-byte aligned
 hipError_t leaf_launch_sat_check16(const void* const* bufs, const size_t* numel, int n, float* scaler, float* poison, hipStream_t s);

@@ -112,6 +112,61 @@ __global__ __launch_bounds__(256) void fare_rows_kernel(const float* __restrict_
     }
 }
 
+// Cosine head of text embedding inversion (src/pez/optim_utils.py:191-196 with one prompt and one target; open_clip_pez/model.py:
+// 237-242): c = <f, t> / (||f|| ||t||), loss_b = w (1 - c), and the gradient of the SUM over b (independent inversions)
+//   dout = -w (t / (||f|| ||t||) - c f / ||f||^2)
+// in fp32; the target is normalised here.  Same partials as fare_rows_kernel ({row loss, row max|dout|}), so fare_reduce_kernel
+// chooses the loss scale of the fp16 gradient path from them.
+__global__ __launch_bounds__(256) void cos_rows_kernel(const float* __restrict__ feat, const float* __restrict__ target, int D,
+                                                       float w, float* __restrict__ dout, float* __restrict__ partial,
+                                                       float* __restrict__ cos_out) {
+    leaf_fp16_sat_mode();
+    __shared__ float red[16];
+    const int tid = threadIdx.x, b = blockIdx.x;
+    constexpr int PER = 8;                      // D <= 2048
+    float f[PER], t[PER];
+    float ff = 0.f, tt = 0.f, ft = 0.f;
+#pragma unroll
+    for (int u = 0; u < PER; ++u) {
+        const int j = tid + 256 * u;
+        f[u] = 0.f; t[u] = 0.f;
+        if (j < D) {
+            f[u] = feat[(size_t)b * D + j];
+            t[u] = target[(size_t)b * D + j];
+            ff = fmaf(f[u], f[u], ff);
+            tt = fmaf(t[u], t[u], tt);
+            ft = fmaf(f[u], t[u], ft);
+        }
+    }
+    ff = wave_sum(ff); tt = wave_sum(tt); ft = wave_sum(ft);
+    if ((tid & 63) == 0) { red[tid >> 6] = ff; red[4 + (tid >> 6)] = tt; red[8 + (tid >> 6)] = ft; }
+    __syncthreads();
+    ff = (red[0] + red[1]) + (red[2] + red[3]);
+    tt = (red[4] + red[5]) + (red[6] + red[7]);
+    ft = (red[8] + red[9]) + (red[10] + red[11]);
+    const float inv_f = 1.0f / sqrtf(ff), inv_t = 1.0f / sqrtf(tt);
+    const float c = ft * inv_f * inv_t;
+    const float kt = -w * inv_f * inv_t, kf = w * c * inv_f * inv_f;
+    float amax = 0.f;
+#pragma unroll
+    for (int u = 0; u < PER; ++u) {
+        const int j = tid + 256 * u;
+        if (j < D) {
+            const float go = kt * t[u] + kf * f[u];
+            amax = fmaxf(amax, fabsf(go));
+            dout[(size_t)b * D + j] = go;
+        }
+    }
+    amax = wave_max(amax);
+    if ((tid & 63) == 0) red[12 + (tid >> 6)] = amax;
+    __syncthreads();
+    if (tid == 0) {
+        partial[2 * b] = w * (1.0f - c);
+        partial[2 * b + 1] = fmaxf(fmaxf(red[12], red[13]), fmaxf(red[14], red[15]));
+        if (cos_out) cos_out[b] = c;
+    }
+}
+
 // in place: x[b] /= max(||x[b]||, 1e-12) and norms[b] = ||x[b]||   (F.normalize of the training features, one wave per row)
 __global__ __launch_bounds__(256) void normalize_rows_kernel(float* __restrict__ x, float* __restrict__ norms, int M, int D) {
     leaf_fp16_sat_mode();
@@ -775,6 +830,16 @@ hipError_t leaf_launch_fare_loss(const float* feat, const float* anchor, int B, 
     float* partial = gscale + 64;   // [B][2] right behind the {S, 1/S} slot (carve_bwd reserves it)
     hipLaunchKernelGGL(fare_rows_kernel, dim3(B), dim3(256), 0, s, feat, anchor, B, D, scale, dout, partial, norms);
     hipLaunchKernelGGL(fare_reduce_kernel, dim3(1), dim3(256), 0, s, partial, B, loss, gscale, use_scaling, scaler);
+    return hipGetLastError();
+}
+
+hipError_t leaf_launch_cos_loss(const float* feat, const float* target, int B, int D, float weight, float* cos_out,
+                                float* dout, float* gscale, int use_scaling, hipStream_t s) {
+    if (D > 2048 || B < 1) return hipErrorInvalidValue;
+    float* partial = gscale + 64;   // as leaf_launch_fare_loss
+    hipLaunchKernelGGL(cos_rows_kernel, dim3(B), dim3(256), 0, s, feat, target, D, weight, dout, partial, cos_out);
+    hipLaunchKernelGGL(fare_reduce_kernel, dim3(1), dim3(256), 0, s, partial, B, (float*)nullptr, gscale, use_scaling,
+                       (const float*)nullptr);
     return hipGetLastError();
 }
 

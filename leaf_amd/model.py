@@ -316,6 +316,7 @@ class LeafCLIPText:
         if "logit_scale" in sd:
             self.logit_scale = torch.as_tensor(sd["logit_scale"], dtype=torch.float32).to(self.device)
         self._packed = False
+        self._vocab_inv = None
         return self
 
     def state_dict(self) -> Dict[str, torch.Tensor]:
@@ -392,6 +393,7 @@ class LeafCLIPText:
         self.logit_scale = other.logit_scale.clone()
         self.extra_state = dict(other.extra_state)
         self._packed = False
+        self._vocab_inv = None
         return self
 
     def pack(self):
@@ -682,8 +684,11 @@ class LeafCLIPText:
     def zero_grad(self):
         self.grads.zero_()
 
-    def forward_train(self, text, seq_lens=None, delta: Optional[torch.Tensor] = None, normalize: bool = False) -> torch.Tensor:
-        """Training-mode forward that keeps the activation stash.  ``delta`` (optional embedding-space PGD mode, SURVEY 8a
+    def forward_train(self, text, seq_lens=None, delta: Optional[torch.Tensor] = None, normalize: bool = False,
+                      pool_last: bool = False) -> torch.Tensor:
+        """Training-mode forward that keeps the activation stash.  ``pool_last`` (text embedding inversion, leaf_amd/inversion.py):
+        pool at row ``seq_lens[i] - 1`` and keep all ``seq_lens[i]`` rows whatever the ids are -- an inverted prompt may hold
+        EOT / SOT ids anywhere (include/leaf_hip.h, leaf_text_forward_train_last); needs ``seq_lens``, excludes ``delta``.  ``delta`` (optional embedding-space PGD mode, SURVEY 8a
         row a12): fp32 CUDA tensor [rows, width] in the PACKED row layout of this call (``rows_of(seq_lens)`` rows; dense
         [N * ctx, width] when rows are not trimmed), added to the token embeddings.  ``normalize`` = --normalize_fare
         (utils_AT.py:319): returns F.normalize(features); the following ``backward`` differentiates through it."""
@@ -700,6 +705,14 @@ class LeafCLIPText:
         stash = self._grow("stash", self._lib.leaf_text_stash_bytes(self._h, n))
         out = torch.empty(n, self.cfg.embed_dim, dtype=torch.float32, device=self.device)
         ws = self._workspace(2, n)
+        if pool_last:
+            if delta is not None or seq_lens is None or keep is None:
+                raise ValueError("pool_last needs explicit seq_lens (and row trimming on) and takes no delta")
+            _lib.check(self._lib.leaf_text_forward_train_last(self._h, _ptr(self.flat), _ptr(self.w16), _ptr(t), lens_p, _ptr(cu), n,
+                                                              _ptr(out), _ptr(stash), stash.numel(), _ptr(ws), ws.numel(),
+                                                              self._stream()), "leaf_text_forward_train_last")
+            self._train_tokens = t
+            return out
         if delta is not None:
             rows = int(keep.sum()) if keep is not None else n * self.cfg.context_length
             if delta.dtype != torch.float32 or not delta.is_contiguous() or delta.numel() != rows * self.cfg.width:
@@ -728,6 +741,49 @@ class LeafCLIPText:
                                                       _ptr(self._buf["stash"]), _ptr(g), _ptr(loss), _ptr(ws), ws.numel(),
                                                       self._stream()), "leaf_textfare_input_grad")
         return loss, g
+
+    def cosine_input_grad(self, feat: torch.Tensor, target: torch.Tensor, loss_weight: float = 1.0):
+        """Cosine head of text embedding inversion on the stash of the last ``forward_train``: per sequence b the loss
+        ``loss_weight (1 - cos(feat_b, target_b))`` and the gradient of the SUM over b with respect to the token embeddings, so
+        every sequence gets the gradient of its own loss (src/pez/optim_utils.py:191-196 for one prompt and one target).
+        Returns (cos fp32 [n], d_embed fp32 [rows, width] packed)."""
+        t = self._train_tokens
+        n = t.shape[0]
+        lens_p, cu, keep = self._train_plan
+        rows = int(keep.sum()) if keep is not None else n * self.cfg.context_length
+        target = target.to(device=self.device, dtype=torch.float32).contiguous()
+        if tuple(target.shape) != (n, self.cfg.embed_dim) or tuple(feat.shape) != (n, self.cfg.embed_dim):
+            raise ValueError(f"feat and target must be [{n}, {self.cfg.embed_dim}]")
+        cos = torch.empty(n, dtype=torch.float32, device=self.device)
+        g = torch.empty(rows, self.cfg.width, dtype=torch.float32, device=self.device)
+        ws = self._workspace(2, n)
+        _lib.check(self._lib.leaf_cosine_input_grad(self._h, _ptr(self.flat), _ptr(self.w16_bwd), _ptr(t), lens_p, _ptr(cu), n,
+                                                    _ptr(feat.contiguous()), _ptr(target), float(loss_weight),
+                                                    _ptr(self._buf["stash"]), _ptr(g), _ptr(cos), _ptr(ws), ws.numel(),
+                                                    self._stream()), "leaf_cosine_input_grad")
+        return cos, g
+
+    def nn_project(self, embeds: torch.Tensor):
+        """PEZ's projection step (nn_project, src/pez/optim_utils.py:26-55): for every row of ``embeds`` [M, width] the id of the
+        cosine-nearest row of the token-embedding table and that cosine, on the device: (ids int32 [M], cos fp32 [M]).  The
+        table's inverse row norms are computed once per weight version (``load_state_dict`` / ``adamw_step`` / ``copy_from``
+        drop them)."""
+        d, V = self.cfg.width, self.cfg.vocab_size
+        if embeds.device != self.device or embeds.dtype != torch.float32 or embeds.dim() != 2 or embeds.shape[1] != d:
+            raise ValueError(f"embeds must be fp32 [M, {d}] on {self.device}")
+        q = embeds.contiguous()
+        M = q.shape[0]
+        table = self.params["token_embedding.weight"]
+        if getattr(self, "_vocab_inv", None) is None:
+            inv = torch.empty(V, dtype=torch.float32, device=self.device)
+            _lib.check(self._lib.leaf_vocab_inv_norms(_ptr(table), V, d, _ptr(inv), self._stream()), "leaf_vocab_inv_norms")
+            self._vocab_inv = inv
+        ids = torch.empty(M, dtype=torch.int32, device=self.device)
+        cos = torch.empty(M, dtype=torch.float32, device=self.device)
+        ws = self._grow(("ws", "nnproj"), self._lib.leaf_nn_project_ws_bytes(M, V))
+        _lib.check(self._lib.leaf_nn_project(_ptr(q), M, _ptr(table), _ptr(self._vocab_inv), V, d, _ptr(ids), _ptr(cos), _ptr(ws),
+                                             ws.numel(), self._stream()), "leaf_nn_project")
+        return ids, cos
 
     def pgd_step(self, delta: torch.Tensor, grad: torch.Tensor, alpha: float, eps: float, norm: str = "linf"):
         """In-place fused update of the resident perturbation for the rows of the last ``forward_train``:
@@ -788,6 +844,7 @@ class LeafCLIPText:
         really applied (kept on the device: a skipped step does not advance them, as torch's per-parameter ``step``).
         Returns the 0-d total-norm tensor when clipping or guarding, else None; ``skipped_steps()`` counts skipped steps."""
         self.opt_step += 1
+        self._vocab_inv = None      # nn_project's table norms belong to the weights before this step
         # with the gradient scaler attached a saturated backward has poisoned the gradient with a NaN that only the guard stops
         guard = guard or getattr(self, "_scaler_attached", False)
         if max_norm is not None or guard:
