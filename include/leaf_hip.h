@@ -461,6 +461,28 @@ int leaf_op_attention_bwd(const void* qkv, int qkv_dtype, const void* dout_bf16,
 /* attention backward with an explicit gradient dtype (LEAF_DTYPE_*) for dout / dqkv */
 int leaf_op_attention_bwd_t(const void* qkv, int qkv_dtype, const void* dout16, void* dqkv16, int g_dtype, int n_seq,
                             int ctx, int heads, int width, leaf_stream_t s);
+/* the same on the row map of the training backward: cu [n_seq + 1] on the device = packed rows, NULL = dense (ctx rows per sequence) */
+int leaf_op_attention_bwd_map(const void* qkv, int qkv_dtype, const void* dout16, void* dqkv16, int g_dtype, const int32_t* cu,
+                              int n_seq, int ctx, int heads, int width, leaf_stream_t s);
+/* The other launchers of the training backward one at a time, on the same row map (cu as above; all pointers device pointers).
+ * pool_project_bwd: backward of text_projection + ln_final on the pooled rows.  dout [n_seq, D], pooled [n_seq, d] = LN_final of row
+ * eot_idx[s] of sequence s of x [rows, d]; dx [rows, d]: ONLY the pooled rows are written, with S * d loss / d x (gscale = {S, 1/S});
+ * dproj [d, D], dg [d], db [d] are added to, un-scaled, and may be NULL (all three: input gradient only); scratch: n_seq (d + 2) floats.
+ * embed_bwd: dtok [vocab, d] += (1 / S) sum of the dx rows of each token id (ids clamped to 0 .. vocab - 1; tokens [n_seq, ctx], on
+ * packed rows only the first len(s) slots of a sequence count), dpos [ctx, d] += (1 / S) sum over sequences; rows = rows of dx.
+ * fare_loss: loss = mean_b ||feat_b - anchor_b||^2 * scale, dout = its gradient (through F.normalize when norms [B] = the norms of
+ * the un-normalised features is given), gscale_ws [64 + 2 B]: {S, 1/S} in front, S = 1 without use_scaling, else the power of two
+ * that brings max|dout| into [8, 16), times 2^scaler[LEAF_SC_BACKOFF] when scaler is given.  D <= 2048.
+ * sat_check16: n <= 5 fp16 tensors (HOST arrays of device pointers / element counts; 16-byte aligned, numel % 8 == 0): any
+ * |value| >= 65504 or non-finite raises scaler[LEAF_SC_SAT_FLAG] = 1 and stores NaN to *poison. */
+int leaf_op_pool_project_bwd(const float* dout, const float* pooled, const float* x, const int32_t* eot_idx, const float* g, float eps,
+                             const float* proj, float* dx, float* dproj, float* dg, float* db, const float* gscale, const int32_t* cu,
+                             int n_seq, int ctx, int d, int D, float* scratch, leaf_stream_t s);
+int leaf_op_embed_bwd(const float* dx, const float* gscale, const int32_t* tokens, float* dtok, float* dpos, const int32_t* cu,
+                      int rows, int n_seq, int ctx, int d, int vocab, leaf_stream_t s);
+int leaf_op_fare_loss(const float* feat, const float* anchor, const float* norms, const float* scaler, int B, int D, float scale,
+                      int use_scaling, float* loss, float* dout, float* gscale_ws, leaf_stream_t s);
+int leaf_op_sat_check16(const void* const* bufs, const size_t* numel, int n, float* scaler, float* poison, leaf_stream_t s);
 /* one problem of the grouped weight-gradient kernel: dW[Nw,Kw] += alpha dY^T X, db[Nw] += alpha colsum(dY)
  * (dY [rows,Nw] in g_dtype, X [rows,Kw] in x_dtype, alpha a device scalar or NULL = 1; Nw, Kw multiples of 128) */
 int leaf_op_wgrad(const void* dY, const void* X, float* dW, float* db, int rows, int Nw, int Kw, int x_dtype,

@@ -151,6 +151,12 @@ _SIGS = {
                                     C.c_int, C.c_void_p]),
     "leaf_op_attention_bwd_t": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
                                          C.c_int, C.c_void_p]),
+    "leaf_op_attention_bwd_map": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int,
+                                           C.c_int, C.c_int, C.c_void_p]),
+    "leaf_op_pool_project_bwd": (C.c_int, [C.c_void_p] * 5 + [C.c_float] + [C.c_void_p] * 7 + [C.c_int] * 4 + [C.c_void_p, C.c_void_p]),
+    "leaf_op_embed_bwd": (C.c_int, [C.c_void_p] * 6 + [C.c_int] * 5 + [C.c_void_p]),
+    "leaf_op_fare_loss": (C.c_int, [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_float, C.c_int] + [C.c_void_p] * 4),
+    "leaf_op_sat_check16": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "leaf_op_wgrad": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                C.c_void_p, C.c_void_p]),
     "leaf_op_layernorm_bwd_ws_bytes": (C.c_size_t, [C.c_int, C.c_int]),

@@ -651,6 +651,13 @@ extern "C" int leaf_op_attention_bwd_t(const void* qkv, int qkv_dtype, const voi
     return leaf_check(leaf_launch_attention_bwd(qkv, qkv_dtype, dout16, dqkv16, g_dtype, n_seq,
                                                 RowMap{nullptr, 0, 0, ctx, nullptr, nullptr, 1}, heads, width, (hipStream_t)s), "attention_bwd");
 }
+// ... and on packed rows (cu [n_seq + 1] on the device, NULL = dense): the RowMap of backward_impl (tests/test_gpu_backward_rows.py)
+extern "C" int leaf_op_attention_bwd_map(const void* qkv, int qkv_dtype, const void* dout16, void* dqkv16, int g_dtype,
+                                         const int32_t* cu, int n_seq, int ctx, int heads, int width, leaf_stream_t s) {
+    if (!qkv || !dout16 || !dqkv16 || n_seq < 1) { leaf_set_error("null/invalid argument"); return 1; }
+    return leaf_check(leaf_launch_attention_bwd(qkv, qkv_dtype, dout16, dqkv16, g_dtype, n_seq,
+                                                RowMap{cu, 0, 0, ctx, nullptr, nullptr, 1}, heads, width, (hipStream_t)s), "attention_bwd_map");
+}
 extern "C" int leaf_op_wgrad(const void* dY, const void* X, float* dW, float* db, int rows, int Nw, int Kw, int x_dtype,
                              int g_dtype, const float* alpha_dev, leaf_stream_t s) {
     if (!leaf_wgrad_tn_ok(Nw, Kw, Nw, Kw)) { leaf_set_error("wgrad needs Nw, Kw multiples of 128"); return 1; }

@@ -343,6 +343,42 @@ extern "C" int leaf_op_cosine_head(const float* feat, const float* target, int B
     return leaf_check(leaf_launch_cos_loss(feat, target, B, D, loss_weight, cos_out, dout, ws, 0, (hipStream_t)s), "cosine_head");
 }
 
+// ---- the launchers of backward_impl one at a time, on the RowMap it builds (kernel hooks of tests/test_gpu_backward_rows.py): no
+// logic of their own
+extern "C" int leaf_op_pool_project_bwd(const float* dout, const float* pooled, const float* x, const int32_t* eot_idx, const float* g,
+                                        float eps, const float* proj, float* dx, float* dproj, float* dg, float* db,
+                                        const float* gscale, const int32_t* cu, int n_seq, int ctx, int d, int D, float* scratch,
+                                        leaf_stream_t s) {
+    if (!dout || !pooled || !x || !eot_idx || !g || !proj || !dx || !gscale || !scratch || n_seq < 1 || D < 1 ||
+        (dg == nullptr) != (db == nullptr)) { leaf_set_error("null/invalid argument"); return 1; }
+    return leaf_check(leaf_launch_pool_project_bwd(dout, pooled, x, eot_idx, g, nullptr, eps, proj, dx, dproj, dg, db, gscale, n_seq,
+                                                   RowMap{cu, 0, 0, ctx, nullptr, nullptr, 1}, d, D, scratch, (hipStream_t)s),
+                      "pool_project_bwd");
+}
+
+extern "C" int leaf_op_embed_bwd(const float* dx, const float* gscale, const int32_t* tokens, float* dtok, float* dpos,
+                                 const int32_t* cu, int rows, int n_seq, int ctx, int d, int vocab, leaf_stream_t s) {
+    if (!dx || !gscale || !tokens || !dtok || !dpos || rows < 1 || n_seq < 1 || ctx < 1 || d < 1 || vocab < 1) {
+        leaf_set_error("null/invalid argument");
+        return 1;
+    }
+    return leaf_check(leaf_launch_embed_bwd(dx, gscale, tokens, dtok, dpos, rows, n_seq, RowMap{cu, 0, 0, ctx, nullptr, nullptr, 1}, d,
+                                            vocab, (hipStream_t)s), "embed_bwd");
+}
+
+// gscale_ws: 64 + 2 B floats, {S, 1/S} in front (as leaf_op_cosine_head); norms / scaler may be NULL
+extern "C" int leaf_op_fare_loss(const float* feat, const float* anchor, const float* norms, const float* scaler, int B, int D,
+                                 float scale, int use_scaling, float* loss, float* dout, float* gscale_ws, leaf_stream_t s) {
+    if (!feat || !anchor || !gscale_ws || B < 1 || D < 1) { leaf_set_error("null/invalid argument"); return 1; }
+    return leaf_check(leaf_launch_fare_loss(feat, anchor, B, D, scale, loss, dout, gscale_ws, use_scaling, (hipStream_t)s, norms, scaler),
+                      "fare_loss");
+}
+
+extern "C" int leaf_op_sat_check16(const void* const* bufs, const size_t* numel, int n, float* scaler, float* poison, leaf_stream_t s) {
+    if (!bufs || !numel) { leaf_set_error("null/invalid argument"); return 1; }
+    return leaf_check(leaf_launch_sat_check16(bufs, numel, n, scaler, poison, (hipStream_t)s), "sat_check16");
+}
+
 extern "C" int leaf_vocab_inv_norms(const float* table, int V, int d, float* inv_norm, leaf_stream_t s) {
     if (!table || !inv_norm || V < 1) { leaf_set_error("vocab_inv_norms: null/invalid argument"); return 1; }
     if (!leaf_nn_project_ok(d)) { leaf_set_error("vocab_inv_norms: d = %d must be a multiple of 4, at most 2048", d); return 1; }

@@ -5,7 +5,7 @@ import numpy as np
 import pytest
 
 from oracle import text_oracle as O
-from tests.util import attn_seq_ref, launch_families, ptr, rel_l2, row_rel_l2, stream, to16
+from tests.util import attn_seq_ref, launch_families, ln_bwd_ref, ptr, rel_l2, row_rel_l2, stream, to16
 
 pytestmark = pytest.mark.gpu
 DT = {"bf16": 0, "fp16": 1}
@@ -214,11 +214,7 @@ def test_wgrad_group(env, xdt, gdt, rows, Nw, Kw):
     assert rel_l2(tb.cpu().numpy(), want_b) < 2e-6
 
 
-@pytest.mark.parametrize("with_params", [True, False])
-@pytest.mark.parametrize("rows,d", [(3219, 768), (800, 1024), (130, 1280), (7, 128), (40, 2048)])
-def test_layernorm_bwd(env, with_params, rows, d):
-    """LayerNorm backward (train.hip ln_bwd_kernel: dx += dLN/dx, 16-bit copy, dg / db += column sums / S) against float64
-    numpy; every tower width has its own instantiation (float4 chunks per lane, waves per workgroup)."""
+def _layernorm_bwd_case(env, with_params, rows, d, g16):
     lib, torch, dev = env
     from leaf_amd import _lib
     rng = np.random.default_rng(rows + d)
@@ -228,29 +224,54 @@ def test_layernorm_bwd(env, with_params, rows, d):
     dx0 = rng.standard_normal((rows, d)).astype(np.float32)
     dg0, db0 = rng.standard_normal(d).astype(np.float32), rng.standard_normal(d).astype(np.float32)
     S = 8.0
-    x64, dy64 = x.astype(np.float64), dy.astype(np.float64)
-    mu = x64.mean(-1, keepdims=True)
-    rstd = 1.0 / np.sqrt(x64.var(-1, keepdims=True) + 1e-5)
-    xhat = (x64 - mu) * rstd
-    dxhat = dy64 * g
-    want_dx = dx0 + rstd * (dxhat - dxhat.mean(-1, keepdims=True) - xhat * (dxhat * xhat).mean(-1, keepdims=True))
+    dy64 = dy.astype(np.float64)
+    dln, xhat = ln_bwd_ref(dy, x, g, 1e-5)
+    want_dx = dx0 + dln
     want_dg = dg0 + (dy64 * xhat).sum(0) / S
     want_db = db0 + dy64.sum(0) / S
     tx, tdy, tg, tdx, tdg, tdb = (torch.from_numpy(a.copy()).to(dev) for a in (x, dy, g, dx0, dg0, db0))
-    t16 = torch.zeros(rows, d, dtype=torch.float16, device=dev)
+    t16 = torch.zeros(rows, d, dtype=torch.float16 if g16 == "fp16" else torch.bfloat16, device=dev)
     gs = torch.tensor([S, 1.0 / S], dtype=torch.float32, device=dev)
     ws = torch.empty(lib.leaf_op_layernorm_bwd_ws_bytes(rows, d), dtype=torch.uint8, device=dev)
-    _lib.check(lib.leaf_op_layernorm_bwd(ptr(tdy), ptr(tx), ptr(tg), 1e-5, ptr(tdx), ptr(t16), DT["fp16"], ptr(gs),
+    _lib.check(lib.leaf_op_layernorm_bwd(ptr(tdy), ptr(tx), ptr(tg), 1e-5, ptr(tdx), ptr(t16), DT[g16], ptr(gs),
                                          ptr(tdg) if with_params else None, ptr(tdb) if with_params else None, rows, d,
                                          ptr(ws), ws.numel(), stream()), "layernorm_bwd")
     torch.cuda.synchronize()
     got = tdx.cpu().numpy()
     assert rel_l2(got, want_dx) < 2e-6
-    assert np.array_equal(t16.cpu().numpy(), np.clip(got, -65504, 65504).astype(np.float16))
+    # per row: the same formula in numpy float32 on the same inputs is the error model; 4 x its worst row (the summation orders differ)
+    model = dx0 + ln_bwd_ref(dy, x, g, 1e-5, np.float32)[0]
+    assert model.dtype == np.float32
+    e_model, e_kernel = row_rel_l2(model, want_dx), row_rel_l2(got, want_dx)
+    print(f"LN_BWD rows={rows} d={d} params={with_params}: kernel {e_kernel.max():.3e} model {e_model.max():.3e} "
+          f"ratio {e_kernel.max() / e_model.max():.3f}")
+    assert e_kernel.max() <= 4.0 * e_model.max(), f"row {int(e_kernel.argmax())}: {e_kernel.max():.3e} > 4 x model {e_model.max():.3e}"
+    if g16 == "fp16":
+        assert np.array_equal(t16.cpu().numpy(), np.clip(got, -65504, 65504).astype(np.float16))
+    else:       # the fp32 dx rounded to bf16 by torch
+        assert torch.equal(t16.view(torch.int16), tdx.to(torch.bfloat16).view(torch.int16))
     if with_params:
         assert rel_l2(tdg.cpu().numpy(), want_dg) < 5e-6 and rel_l2(tdb.cpu().numpy(), want_db) < 5e-6
     else:
         assert np.array_equal(tdg.cpu().numpy(), dg0) and np.array_equal(tdb.cpu().numpy(), db0)
+
+
+@pytest.mark.parametrize("with_params", [True, False])
+@pytest.mark.parametrize("rows,d", [(3219, 768), (800, 1024), (130, 1280), (7, 128), (40, 2048), (4100, 128), (4133, 768), (2071, 1280)])
+def test_layernorm_bwd(env, with_params, rows, d):
+    """LayerNorm backward (train.hip ln_bwd_kernel: dx += dLN/dx, 16-bit copy, dg / db += column sums / S) against float64
+    numpy; every tower width has its own instantiation (float4 chunks per lane, waves per workgroup).  The grid is capped at 256
+    workgroups (leaf_ln_bwd_grid): 4100 x 128, 4133 x 768 (16 waves) and 2071 x 1280 (8 waves) are one ragged row group past the cap,
+    so some waves take a second row and their LDS image of the parameter gradients accumulates across rows.
+    Worst row error of the kernel over the worst row error of the float32 model (the bound is 4), measured on an MI355X: 0.86 .. 1.19 over the shapes
+    (7 x 128: 1.19, 4100 x 128: 1.01, 4133 x 768: 1.04, 2071 x 1280: 0.86)."""
+    _layernorm_bwd_case(env, with_params, rows, d, "fp16")
+
+
+@pytest.mark.parametrize("rows,d", [(4133, 768), (40, 2048)])
+def test_layernorm_bwd_bf16_copy(env, rows, d):
+    """the 16-bit copy in the bf16 gradient type: the fp32 dx rounded to bf16 (round to nearest even, as torch rounds it)"""
+    _layernorm_bwd_case(env, True, rows, d, "bf16")
 
 
 @pytest.mark.parametrize("normalize", [0, 1])

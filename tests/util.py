@@ -155,3 +155,121 @@ def lnfold_rows_ref(x16, wp, s_vec, c_vec, mean, rstd, dtype):
     f = lambda a: np.asarray(a, np.float64)
     acc = f(x16) @ f(wp).T
     return round16(f(rstd)[:, None] * (acc - f(mean)[:, None] * f(s_vec)[None, :]) + f(c_vec)[None, :], dtype)
+
+
+# ---------------------------------------------------------------- float64 references of the training backward's kernels on packed rows
+# (leaf_amd/csrc/attention_bwd.hip, train.hip).  Plain numpy, no code shared with leaf_amd/: tests/test_gpu_backward_rows.py and
+# test_layernorm_bwd hold the kernels to them, tests/test_backward_ref_cpu.py pins them against torch autograd / np.add.at.
+def attn_bwd_seq_ref(seq, do, heads, ft, gt, model=None):
+    """Backward of softmax(q k^T / 8 + causal mask) v per head of ONE sequence: seq [T, 3d] q|k|v rows (values of the forward type
+    ft), do [T, d] (values of the gradient type gt) -> [T, 3d] dq|dk|dv in float64.  P comes from the operands as given; when
+    ft != gt, q, k, v are rounded once to gt before the gradient products (the kernel's documented conversion: it is part of the
+    operation, not of the error).  model: the kernel's three roundings to gt on top -- P before P^T dO, dS before its two products,
+    the output."""
+    seq, do = np.asarray(seq, np.float64), np.asarray(do, np.float64)
+    T, d = seq.shape[0], heads * 64
+    q, k, v = (seq[:, i * d:(i + 1) * d].reshape(T, heads, 64).transpose(1, 0, 2) for i in range(3))
+    g = do.reshape(T, heads, 64).transpose(1, 0, 2)
+    s = q @ k.transpose(0, 2, 1) / 8.0 + np.triu(np.full((T, T), -np.inf), 1)
+    p = np.exp(s - s.max(-1, keepdims=True))
+    p /= p.sum(-1, keepdims=True)
+    if ft != gt:
+        q, k, v = round16(q, gt), round16(k, gt), round16(v, gt)
+    dp = g @ v.transpose(0, 2, 1)
+    ds = p * (dp - (p * dp).sum(-1, keepdims=True)) / 8.0
+    if model:
+        p, ds = round16(p, gt), round16(ds, gt)
+    dq, dk, dv = ds @ k, ds.transpose(0, 2, 1) @ q, p.transpose(0, 2, 1) @ g
+    out = np.concatenate([a.transpose(1, 0, 2).reshape(T, d) for a in (dq, dk, dv)], axis=1)
+    return round16(out, gt) if model else out
+
+
+def ln_bwd_ref(dy, x, g, eps, dtype=np.float64):
+    """LayerNorm backward of every row in the arithmetic of `dtype` -> (dx [rows, d], xhat [rows, d]); dg = (dy * xhat).sum(0) and
+    db = dy.sum(0) are the caller's.  dtype = np.float32 is the error MODEL of the fp32 kernels (same formula, same inputs)."""
+    dy, x, g = (np.asarray(a, dtype) for a in (dy, x, g))
+    d = dtype(x.shape[-1])
+    mu = x.sum(-1, keepdims=True, dtype=dtype) / d
+    xc = x - mu
+    rstd = dtype(1) / np.sqrt((xc * xc).sum(-1, keepdims=True, dtype=dtype) / d + dtype(eps))
+    xhat = xc * rstd
+    dxhat = dy * g
+    m1 = dxhat.sum(-1, keepdims=True, dtype=dtype) / d
+    m2 = (dxhat * xhat).sum(-1, keepdims=True, dtype=dtype) / d
+    return rstd * (dxhat - m1 - xhat * m2), xhat
+
+
+def pool_project_bwd_ref(dout, xe, g, b, eps, proj, dtype=np.float64):
+    """The chain behind the loss head: pooled = LN_final(xe) (xe [n, d] = the pooled rows), feat = pooled @ proj [d, D].
+    dout [n, D] -> dict(pooled, dproj [d, D], dpooled [n, d], dx [n, d] (un-scaled), dg [d], db [d]) plus, for the derived
+    accumulation bounds, the sums of absolute terms abs_dproj, abs_dpooled, abs_dg, abs_db."""
+    dout, xe, g, b, proj = (np.asarray(a, dtype) for a in (dout, xe, g, b, proj))
+    dpooled = dout @ proj.T
+    dx, xhat = ln_bwd_ref(dpooled, xe, g, eps, dtype)
+    pooled = xhat * g + b
+    r = dict(pooled=pooled, dproj=pooled.T @ dout, dpooled=dpooled, dx=dx, dg=(dpooled * xhat).sum(0), db=dpooled.sum(0))
+    if dtype is np.float64:
+        mu = xe.mean(-1, keepdims=True)
+        rstd = 1.0 / np.sqrt(((xe - mu) ** 2).mean(-1, keepdims=True) + eps)
+        r["abs_dpooled"] = np.abs(dout) @ np.abs(proj).T
+        r["abs_dproj"] = np.abs(pooled).T @ np.abs(dout)
+        r["abs_dg"] = (r["abs_dpooled"] * (np.abs(xe) + np.abs(mu)) * rstd).sum(0)
+        r["abs_db"] = r["abs_dpooled"].sum(0)
+    return r
+
+
+def embed_bwd_ref(dx, tokens, lens, ctx, vocab):
+    """The embedding scatter on packed rows: dx [sum(lens), d], tokens [n_seq, ctx]; slot (s, p) is KEPT iff p < lens[s], its row is
+    sum(lens[:s]) + p and its id is clamped to 0 .. vocab - 1.  -> (dtok [vocab, d], dpos [ctx, d], abs_dtok, abs_dpos, count
+    [vocab]): sums of the kept rows, sums of their absolute values, kept rows per id.  Dense rows: lens = [ctx] * n_seq."""
+    dx = np.asarray(dx, np.float64)
+    d = dx.shape[1]
+    dtok, dpos = np.zeros((vocab, d)), np.zeros((ctx, d))
+    atok, apos = np.zeros((vocab, d)), np.zeros((ctx, d))
+    count = np.zeros(vocab, np.int64)
+    row = 0
+    for s, L in enumerate(lens):
+        for p in range(int(L)):
+            t = min(max(int(tokens[s][p]), 0), vocab - 1)
+            dtok[t] += dx[row]
+            atok[t] += np.abs(dx[row])
+            dpos[p] += dx[row]
+            apos[p] += np.abs(dx[row])
+            count[t] += 1
+            row += 1
+    assert row == dx.shape[0]
+    return dtok, dpos, atok, apos, count
+
+
+def fare_ref(feat, anchor, scale, norms=None):
+    """TextFARE head (utils_AT.py:319-321): loss = mean_b sum_j (anchor - feat)^2, dout = scale * d loss / d feat [B, D]; with norms
+    [B] (--normalize_fare) feat = f / max(||f||, 1e-12) and dout is the gradient with respect to f, through F.normalize.
+    -> (loss, dout, abs_loss, abs_dout): the last two are the sums of absolute terms behind loss and behind each dout element."""
+    f, a = np.asarray(feat, np.float64), np.asarray(anchor, np.float64)
+    B = f.shape[0]
+    df = f - a
+    loss = (df * df).sum(-1).mean()
+    g = 2.0 / B * scale * df
+    abs_g = np.abs(g)
+    if norms is not None:
+        inv = 1.0 / np.maximum(np.asarray(norms, np.float64), 1e-12)[:, None]
+        dot = (f * g).sum(-1, keepdims=True)
+        abs_g = (np.abs(g) + np.abs(f) * np.abs(f * g).sum(-1, keepdims=True)) * inv
+        g = (g - f * dot) * inv
+    return loss, g, (df * df).sum(-1).mean(), abs_g
+
+
+BWD_LENS = [1, 2, 15, 16, 17, 31, 32, 33, 47, 48, 49, 63, 64, 65, 77, 79, 80, 81, 95, 96]   # every tile count, each boundary +- 1
+
+
+def attn_bwd_pack(seed, lens, heads, ft, gt):
+    """One pack of sequences for the attention backward: standard normal q|k|v [sum(lens), 3d] rounded to ft and dO [sum(lens), d]
+    rounded to gt (float64 arrays), with the float64 reference and the rounding model of every sequence, concatenated."""
+    rng = np.random.default_rng(seed)
+    rows, d = int(sum(lens)), heads * 64
+    qkv = round16(rng.standard_normal((rows, 3 * d)).astype(np.float32), ft)
+    do = round16(rng.standard_normal((rows, d)).astype(np.float32), gt)
+    cu = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+    exact = np.concatenate([attn_bwd_seq_ref(qkv[a:b], do[a:b], heads, ft, gt) for a, b in zip(cu[:-1], cu[1:])])
+    model = np.concatenate([attn_bwd_seq_ref(qkv[a:b], do[a:b], heads, ft, gt, model=True) for a, b in zip(cu[:-1], cu[1:])])
+    return qkv, do, exact, model
