@@ -261,6 +261,22 @@ int leaf_textfare_backward_events(leaf_text_t h, const float* params, const void
                                   const float* anchor, float accum_scale, const void* stash, float* grads, float* loss_out,
                                   void* ws, size_t ws_bytes, leaf_stream_t s, void* const* layer_events);
 
+/* Backward from ANY upstream gradient: the caller computed a loss of the features that the last training forward returned (feat,
+ * fp32 [n_seq, embed_dim]) and hands over dfeat = d loss / d feat (fp32 [n_seq, embed_dim], device).  Back-propagates scale * dfeat
+ * through the stash of that forward -- through F.normalize as well when option normalize_fare is on (feat is then the normalised
+ * rows; it is read for that product only).  grads (flat fp32, parameter layout; may be NULL): the parameter gradients are
+ * ACCUMULATED (+=), as everywhere else.  d_embed (fp32 [rows, width], packed like the activations; may be NULL): OVERWRITTEN with the
+ * gradient with respect to the token embeddings / delta.  Both may be given (one pass); giving neither, or a NULL dfeat, is an error
+ * reported before any HIP call.  With a scaler state attached and grads given, the fp16 gradient path checks its 16-bit tensors for
+ * saturation and poisons gradient element 0, exactly as the TextFARE backward does (GRADIENT SCALER below); a non-finite dfeat
+ * reaches the gradients as NaN and the guarded optimizer step skips.  layer_events: NULL, or L + 1 events as in
+ * leaf_textfare_backward_events.  Every kernel behind the head is the one the TextFARE and cosine backwards run: fed the dout of
+ * those heads (kernel hooks leaf_op_fare_loss / leaf_op_cosine_head) and scale = 1, it writes their gradients bit for bit. */
+int leaf_text_backward(leaf_text_t h, const float* params, const void* w16_bwd, const int32_t* tokens, const int32_t* seq_lens,
+                       const int32_t* cu_rows, int n_seq, const float* feat, const float* dfeat, float scale, const void* stash,
+                       float* grads /* may be NULL */, float* d_embed /* may be NULL */, void* ws, size_t ws_bytes, leaf_stream_t s,
+                       void* const* layer_events /* may be NULL */);
+
 /* torch.optim.AdamW step over the flat buffers (train_AT_text_only.py:326-341): decoupled weight decay `wd`
  * on the first n_decay elements, 0 on the rest; step counts from 1; grads are multiplied by grad_scale first
  * (1/world_size after a sum all-reduce). */
@@ -290,7 +306,7 @@ enum {
     LEAF_SC_BC1 = 9, LEAF_SC_SQRT_BC2 = 10, /* bias corrections of the last applied step */
     LEAF_SC_WORDS = 16
 };
-/* attach (or detach with NULL) the scaler state used by leaf_textfare_backward* of this handle */
+/* attach (or detach with NULL) the scaler state used by leaf_textfare_backward* and leaf_text_backward of this handle */
 int leaf_text_set_grad_scaler(leaf_text_t h, float* state);
 
 /* the same step preceded by torch.nn.utils.clip_grad_norm_(parameters, max_norm, 2.0) (--grad-clip-norm,
@@ -473,6 +489,9 @@ int leaf_op_attention_bwd_map(const void* qkv, int qkv_dtype, const void* dout16
  * fare_loss: loss = mean_b ||feat_b - anchor_b||^2 * scale, dout = its gradient (through F.normalize when norms [B] = the norms of
  * the un-normalised features is given), gscale_ws [64 + 2 B]: {S, 1/S} in front, S = 1 without use_scaling, else the power of two
  * that brings max|dout| into [8, 16), times 2^scaler[LEAF_SC_BACKOFF] when scaler is given.  D <= 2048.
+ * upstream_head: the head of leaf_text_backward alone: dout = scale * dfeat [B, D], through the VJP of F.normalize when feat [B, D] (the
+ * normalised rows) and norms [B] are given (both NULL: none), dout = (g - feat (feat . g)) / max(norms, 1e-12) with g = scale * dfeat;
+ * gscale_ws, use_scaling and scaler as fare_loss.  B >= 1, 1 <= D <= 2048 (an error otherwise, reported before any HIP call).
  * sat_check16: n <= 5 fp16 tensors (HOST arrays of device pointers / element counts; 16-byte aligned, numel % 8 == 0): any
  * |value| >= 65504 or non-finite raises scaler[LEAF_SC_SAT_FLAG] = 1 and stores NaN to *poison. */
 int leaf_op_pool_project_bwd(const float* dout, const float* pooled, const float* x, const int32_t* eot_idx, const float* g, float eps,
@@ -482,6 +501,8 @@ int leaf_op_embed_bwd(const float* dx, const float* gscale, const int32_t* token
                       int rows, int n_seq, int ctx, int d, int vocab, leaf_stream_t s);
 int leaf_op_fare_loss(const float* feat, const float* anchor, const float* norms, const float* scaler, int B, int D, float scale,
                       int use_scaling, float* loss, float* dout, float* gscale_ws, leaf_stream_t s);
+int leaf_op_upstream_head(const float* dfeat, const float* feat, const float* norms, const float* scaler, int B, int D, float scale,
+                          int use_scaling, float* dout, float* gscale_ws, leaf_stream_t s);
 int leaf_op_sat_check16(const void* const* bufs, const size_t* numel, int n, float* scaler, float* poison, leaf_stream_t s);
 /* one problem of the grouped weight-gradient kernel: dW[Nw,Kw] += alpha dY^T X, db[Nw] += alpha colsum(dY)
  * (dY [rows,Nw] in g_dtype, X [rows,Kw] in x_dtype, alpha a device scalar or NULL = 1; Nw, Kw multiples of 128) */

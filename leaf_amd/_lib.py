@@ -90,6 +90,9 @@ _SIGS = {
     "leaf_textfare_backward_events": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                 C.c_int, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p,
                                                 C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "leaf_text_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                     C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
+                                     C.c_void_p]),
     "leaf_clip_grads_inplace": (C.c_int, [C.c_void_p, C.c_size_t, C.c_float, C.c_float, C.c_void_p, C.c_void_p]),
     "leaf_adamw_step_clip": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_float,
                                       C.c_float, C.c_float, C.c_float, C.c_float, C.c_int, C.c_float, C.c_float,
@@ -156,6 +159,7 @@ _SIGS = {
     "leaf_op_pool_project_bwd": (C.c_int, [C.c_void_p] * 5 + [C.c_float] + [C.c_void_p] * 7 + [C.c_int] * 4 + [C.c_void_p, C.c_void_p]),
     "leaf_op_embed_bwd": (C.c_int, [C.c_void_p] * 6 + [C.c_int] * 5 + [C.c_void_p]),
     "leaf_op_fare_loss": (C.c_int, [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_float, C.c_int] + [C.c_void_p] * 4),
+    "leaf_op_upstream_head": (C.c_int, [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_float, C.c_int] + [C.c_void_p] * 3),
     "leaf_op_sat_check16": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "leaf_op_wgrad": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                C.c_void_p, C.c_void_p]),

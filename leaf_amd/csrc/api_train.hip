@@ -174,9 +174,11 @@ extern "C" int leaf_text_forward_train(leaf_text_t h, const float* P, const void
 }
 
 // The loss whose gradient the backward starts from: TextFARE against an anchor (ref = anchor, scale = accum_scale, out = the
-// loss, one float) or the cosine head of text embedding inversion (ref = target, scale = loss_weight, out = cos [n_seq]).
+// loss, one float), the cosine head of text embedding inversion (ref = target, scale = loss_weight, out = cos [n_seq]) or a loss
+// the caller computed itself (ref = dfeat = its d loss / d feat, scale = a factor on it, out unused).
+enum HeadKind { HEAD_FARE, HEAD_COSINE, HEAD_UPSTREAM };
 struct LossHead {
-    bool cosine;
+    HeadKind kind;
     const float* ref;
     float scale;
     float* out;
@@ -209,8 +211,11 @@ static int backward_impl(leaf_text_t h, const float* P, const void* w16_bwd, con
     const float* inv_s = b.gscale + 1;
     const uint16_t* WT = (const uint16_t*)w16_bwd;
 
-    if (head.cosine)
+    if (head.kind == HEAD_COSINE)
         LEAF_TRY(leaf_launch_cos_loss(feat, head.ref, n_seq, D, head.scale, head.out, b.dout, b.gscale, gk == 1, s));
+    else if (head.kind == HEAD_UPSTREAM)
+        LEAF_TRY(leaf_launch_upstream_grad(head.ref, feat, n_seq, D, head.scale, b.dout, b.gscale, gk == 1, s,
+                                           h->normalize_fare ? st.norms : nullptr, h->scaler));
     else
         LEAF_TRY(leaf_launch_fare_loss(feat, head.ref, n_seq, D, head.scale, head.out, b.dout, b.gscale, gk == 1, s,
                                        h->normalize_fare ? st.norms : nullptr, h->scaler));
@@ -300,7 +305,7 @@ extern "C" int leaf_textfare_backward(leaf_text_t h, const float* P, const void*
                                       const void* stash, float* G, float* loss_out, void* ws, size_t ws_bytes,
                                       leaf_stream_t s_) {
     if (!G) { leaf_set_error("null/invalid argument"); return 1; }
-    return backward_impl(h, P, w16_bwd, tokens, seq_lens, cu_rows, n_seq, feat, LossHead{false, anchor, accum_scale, loss_out}, stash, G,
+    return backward_impl(h, P, w16_bwd, tokens, seq_lens, cu_rows, n_seq, feat, LossHead{HEAD_FARE, anchor, accum_scale, loss_out}, stash, G,
                          nullptr, ws, ws_bytes, s_);
 }
 
@@ -313,7 +318,7 @@ extern "C" int leaf_textfare_backward_events(leaf_text_t h, const float* P, cons
                                              float* loss_out, void* ws, size_t ws_bytes, leaf_stream_t s_,
                                              void* const* layer_events) {
     if (!G) { leaf_set_error("null/invalid argument"); return 1; }
-    return backward_impl(h, P, w16_bwd, tokens, seq_lens, cu_rows, n_seq, feat, LossHead{false, anchor, accum_scale, loss_out}, stash, G,
+    return backward_impl(h, P, w16_bwd, tokens, seq_lens, cu_rows, n_seq, feat, LossHead{HEAD_FARE, anchor, accum_scale, loss_out}, stash, G,
                          nullptr, ws, ws_bytes, s_, layer_events);
 }
 
@@ -322,7 +327,7 @@ extern "C" int leaf_textfare_input_grad(leaf_text_t h, const float* P, const voi
                                         const float* anchor, const void* stash, float* d_embed, float* loss_out, void* ws,
                                         size_t ws_bytes, leaf_stream_t s_) {
     if (!d_embed) { leaf_set_error("null/invalid argument"); return 1; }
-    return backward_impl(h, P, w16_bwd, tokens, seq_lens, cu_rows, n_seq, feat, LossHead{false, anchor, 1.0f, loss_out}, stash, nullptr,
+    return backward_impl(h, P, w16_bwd, tokens, seq_lens, cu_rows, n_seq, feat, LossHead{HEAD_FARE, anchor, 1.0f, loss_out}, stash, nullptr,
                          d_embed, ws, ws_bytes, s_);
 }
 
@@ -332,8 +337,18 @@ extern "C" int leaf_cosine_input_grad(leaf_text_t h, const float* P, const void*
                                       void* ws, size_t ws_bytes, leaf_stream_t s_) {
     if (!d_embed) { leaf_set_error("null/invalid argument"); return 1; }
     if (h && h->normalize_fare) { leaf_set_error("cosine_input_grad: option normalize_fare must be off"); return 1; }
-    return backward_impl(h, P, w16_bwd, tokens, seq_lens, cu_rows, n_seq, feat, LossHead{true, target, loss_weight, cos_out}, stash,
+    return backward_impl(h, P, w16_bwd, tokens, seq_lens, cu_rows, n_seq, feat, LossHead{HEAD_COSINE, target, loss_weight, cos_out}, stash,
                          nullptr, d_embed, ws, ws_bytes, s_);
+}
+
+// Backward from a gradient the caller computed (any loss of the features): parameter gradients, the embedding-input gradient or
+// both in one pass.  backward_impl refuses a NULL dfeat and two NULL outputs before its first HIP call.
+extern "C" int leaf_text_backward(leaf_text_t h, const float* P, const void* w16_bwd, const int32_t* tokens, const int32_t* seq_lens,
+                                  const int32_t* cu_rows, int n_seq, const float* feat, const float* dfeat, float scale,
+                                  const void* stash, float* G, float* d_embed, void* ws, size_t ws_bytes, leaf_stream_t s_,
+                                  void* const* layer_events) {
+    return backward_impl(h, P, w16_bwd, tokens, seq_lens, cu_rows, n_seq, feat, LossHead{HEAD_UPSTREAM, dfeat, scale, nullptr}, stash,
+                         G, d_embed, ws, ws_bytes, s_, layer_events);
 }
 
 // the cosine head alone (kernel hook for the tests): dout [B, D], cos_out [B]; ws = 64 + 2 B floats
@@ -372,6 +387,15 @@ extern "C" int leaf_op_fare_loss(const float* feat, const float* anchor, const f
     if (!feat || !anchor || !gscale_ws || B < 1 || D < 1) { leaf_set_error("null/invalid argument"); return 1; }
     return leaf_check(leaf_launch_fare_loss(feat, anchor, B, D, scale, loss, dout, gscale_ws, use_scaling, (hipStream_t)s, norms, scaler),
                       "fare_loss");
+}
+
+// the upstream-gradient head alone (kernel hook for the tests): gscale_ws as leaf_op_fare_loss; feat / norms NULL = no normalisation
+extern "C" int leaf_op_upstream_head(const float* dfeat, const float* feat, const float* norms, const float* scaler, int B, int D,
+                                     float scale, int use_scaling, float* dout, float* gscale_ws, leaf_stream_t s) {
+    if (!dfeat || !dout || !gscale_ws || B < 1 || D < 1 || (norms && !feat)) { leaf_set_error("upstream_head: null/invalid argument"); return 1; }
+    if (D > 2048) { leaf_set_error("upstream_head: D = %d, at most 2048", D); return 1; }
+    return leaf_check(leaf_launch_upstream_grad(dfeat, feat, B, D, scale, dout, gscale_ws, use_scaling, (hipStream_t)s, norms, scaler),
+                      "upstream_head");
 }
 
 extern "C" int leaf_op_sat_check16(const void* const* bufs, const size_t* numel, int n, float* scaler, float* poison, leaf_stream_t s) {

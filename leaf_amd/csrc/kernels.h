@@ -198,6 +198,11 @@ hipError_t leaf_launch_fare_loss(const float* feat, const float* anchor, int B, 
 // leaf_launch_fare_loss: loss_b = weight (1 - cos(feat_b, target_b)), dout = d (sum_b loss_b) / d feat, cos_out[b] (may be null)
 hipError_t leaf_launch_cos_loss(const float* feat, const float* target, int B, int D, float weight, float* cos_out,
                                 float* dout, float* gscale, int use_scaling, hipStream_t s);
+// upstream-gradient head with the outputs and loss-scale protocol of leaf_launch_fare_loss: dout = scale * dfeat, dfeat [B, D] = the
+// caller's d loss / d feat; with norms (--normalize_fare: feat = the normalised features the forward returned, required then) through
+// the VJP of F.normalize, dout = (g - feat (feat . g)) / max(norms, 1e-12) with g = scale * dfeat.  D <= 2048.
+hipError_t leaf_launch_upstream_grad(const float* dfeat, const float* feat, int B, int D, float scale, float* dout, float* gscale,
+                                     int use_scaling, hipStream_t s, const float* norms = nullptr, const float* scaler = nullptr);
 // fp16 gradient path: raise scaler[LEAF_SC_SAT_FLAG] and poison *poison (gradient element 0) with NaN when any of the n <= 5
 // 16-bit tensors holds a saturated (|x| >= 65504) or non-finite value; numel multiples of 8, pointers 16-byte aligned
 hipError_t leaf_launch_sat_check16(const void* const* bufs, const size_t* numel, int n, float* scaler, float* poison, hipStream_t s);

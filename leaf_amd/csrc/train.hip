@@ -61,6 +61,41 @@ __global__ __launch_bounds__(256) void cast16_kernel(const void* __restrict__ sr
     for (; i < n; i += stride) store16(dst, dkind, i, load_as_f32(src, kind, i));
 }
 
+// Second half of a loss head's row, shared by the heads that differentiate through --normalize_fare: g = d loss / d feat of row b
+// (PER elements per thread, j = tid + 256 u, zero behind D), f = the feature row, s / dot = this thread's share of the row loss
+// and of f . g.  Applies the VJP of F.normalize when norms is given, writes the dout row and the {row loss, row max|dout|}
+// partials; every reduction is a fixed tree (wave sums, then the four wave results pairwise).  red: 12 floats of LDS.
+template <int PER>
+__device__ __forceinline__ void head_row_finish(const float (&g)[PER], const float (&f)[PER], float s, float dot, int b, int D,
+                                                const float* __restrict__ norms, float* __restrict__ dout,
+                                                float* __restrict__ partial, float* red) {
+    const int tid = threadIdx.x;
+    s = wave_sum(s);
+    dot = wave_sum(dot);
+    if ((tid & 63) == 0) { red[tid >> 6] = s; red[8 + (tid >> 6)] = dot; }
+    __syncthreads();
+    // --normalize_fare (utils_AT.py:319): feat = f / ||f||; d f = (d feat - feat (feat . d feat)) / ||f||
+    const float dotb = (red[8] + red[9]) + (red[10] + red[11]);
+    const float inv_n = norms ? 1.0f / fmaxf(norms[b], 1e-12f) : 1.0f;
+    float amax = 0.f;
+#pragma unroll
+    for (int u = 0; u < PER; ++u) {
+        const int j = tid + 256 * u;
+        if (j < D) {
+            const float go = norms ? (g[u] - f[u] * dotb) * inv_n : g[u];
+            amax = fmaxf(amax, fabsf(go));
+            if (dout) dout[(size_t)b * D + j] = go;
+        }
+    }
+    amax = wave_max(amax);
+    if ((tid & 63) == 0) red[4 + (tid >> 6)] = amax;
+    __syncthreads();
+    if (tid == 0) {
+        partial[2 * b] = (red[0] + red[1]) + (red[2] + red[3]);
+        partial[2 * b + 1] = fmaxf(fmaxf(red[4], red[5]), fmaxf(red[6], red[7]));
+    }
+}
+
 // loss = mean_b sum_j (a-f)^2 ; dout = 2 (f-a)/B * scale ; gscale = {S, 1/S}.  Two launches: one block per caption writes
 // its dout row and {row sum, row max|dout|} partials, one block reduces the partials in a fixed order.
 __global__ __launch_bounds__(256) void fare_rows_kernel(const float* __restrict__ feat, const float* __restrict__ anchor,
@@ -86,30 +121,35 @@ __global__ __launch_bounds__(256) void fare_rows_kernel(const float* __restrict_
             dot = fmaf(f[u], g[u], dot);
         }
     }
-    s = wave_sum(s);
-    dot = wave_sum(dot);
-    if ((tid & 63) == 0) { red[tid >> 6] = s; red[8 + (tid >> 6)] = dot; }
-    __syncthreads();
-    // --normalize_fare (utils_AT.py:319): feat = f / ||f||; d f = (d feat - feat (feat . d feat)) / ||f||
-    const float dotb = (red[8] + red[9]) + (red[10] + red[11]);
-    const float inv_n = norms ? 1.0f / fmaxf(norms[b], 1e-12f) : 1.0f;
-    float amax = 0.f;
+    head_row_finish<PER>(g, f, s, dot, b, D, norms, dout, partial, red);
+}
+
+// Upstream-gradient head: the caller (any loss, through autograd) hands over dfeat = d loss / d feat; dout = scale * dfeat, through
+// the VJP of F.normalize when norms is given (feat = the normalised row the training forward returned).  Row loss 0; the same
+// partials as fare_rows_kernel, so fare_reduce_kernel chooses the loss scale of the fp16 gradient path from them.
+__global__ __launch_bounds__(256) void upstream_rows_kernel(const float* __restrict__ dfeat, const float* __restrict__ feat, int D,
+                                                            float scale, float* __restrict__ dout, float* __restrict__ partial,
+                                                            const float* __restrict__ norms) {
+    leaf_fp16_sat_mode();
+    __shared__ float red[12];
+    const int tid = threadIdx.x, b = blockIdx.x;
+    constexpr int PER = 8;                      // D <= 2048
+    float g[PER], f[PER];
+    float dot = 0.f;
 #pragma unroll
     for (int u = 0; u < PER; ++u) {
         const int j = tid + 256 * u;
+        g[u] = 0.f; f[u] = 0.f;
         if (j < D) {
-            const float go = norms ? (g[u] - f[u] * dotb) * inv_n : g[u];
-            amax = fmaxf(amax, fabsf(go));
-            if (dout) dout[(size_t)b * D + j] = go;
+            const size_t i = (size_t)b * D + j;
+            g[u] = scale * dfeat[i];
+            if (norms) {
+                f[u] = feat[i];
+                dot = fmaf(f[u], g[u], dot);
+            }
         }
     }
-    amax = wave_max(amax);
-    if ((tid & 63) == 0) red[4 + (tid >> 6)] = amax;
-    __syncthreads();
-    if (tid == 0) {
-        partial[2 * b] = (red[0] + red[1]) + (red[2] + red[3]);
-        partial[2 * b + 1] = fmaxf(fmaxf(red[4], red[5]), fmaxf(red[6], red[7]));
-    }
+    head_row_finish<PER>(g, f, 0.f, dot, b, D, norms, dout, partial, red);
 }
 
 // Cosine head of text embedding inversion (src/pez/optim_utils.py:191-196 with one prompt and one target; open_clip_pez/model.py:
@@ -840,6 +880,15 @@ hipError_t leaf_launch_cos_loss(const float* feat, const float* target, int B, i
     hipLaunchKernelGGL(cos_rows_kernel, dim3(B), dim3(256), 0, s, feat, target, D, weight, dout, partial, cos_out);
     hipLaunchKernelGGL(fare_reduce_kernel, dim3(1), dim3(256), 0, s, partial, B, (float*)nullptr, gscale, use_scaling,
                        (const float*)nullptr);
+    return hipGetLastError();
+}
+
+hipError_t leaf_launch_upstream_grad(const float* dfeat, const float* feat, int B, int D, float scale, float* dout, float* gscale,
+                                     int use_scaling, hipStream_t s, const float* norms, const float* scaler) {
+    if (D < 1 || D > 2048 || B < 1 || (norms && !feat)) return hipErrorInvalidValue;
+    float* partial = gscale + 64;   // as leaf_launch_fare_loss
+    hipLaunchKernelGGL(upstream_rows_kernel, dim3(B), dim3(256), 0, s, dfeat, feat, D, scale, dout, partial, norms);
+    hipLaunchKernelGGL(fare_reduce_kernel, dim3(1), dim3(256), 0, s, partial, B, (float*)nullptr, gscale, use_scaling, scaler);
     return hipGetLastError();
 }
 

@@ -6,6 +6,7 @@ group first) plus 16-bit MFMA operand copies, and exposes
 * ``encode_text(text, normalize=False)``   -- src/open_clip/model.py:269-284
 * ``score_candidates(tokens, anchor, rho, objective)`` -- one stage of utils_attacks.py:297-393
 * ``forward_train`` / ``backward`` / ``adamw_step``    -- utils_AT.py:317-362
+* ``encode_text_train`` / ``backward_from``            -- the same forward under autograd: any PyTorch loss of the features
 * ``state_dict`` / ``load_state_dict`` with OpenCLIP keys and HF ``CLIPTextModel`` keys
   (conversion/convert_2.py:37-99 key map).
 
@@ -195,6 +196,7 @@ class LeafCLIPText:
         # training state (allocated on demand)
         self.grads = self.exp_avg = self.exp_avg_sq = self.w16_bwd = None
         self.opt_step = 0
+        self.stash_ticket = 0     # bumped by every forward_train: names the forward whose activations the stash holds (backward_from)
         self.rows_scored = 0      # packed rows handed to the scoring passes so far (host-side count; bench.py reports it per rank)
         if trainable:
             self.enable_training()
@@ -693,6 +695,7 @@ class LeafCLIPText:
         [N * ctx, width] when rows are not trimmed), added to the token embeddings.  ``normalize`` = --normalize_fare
         (utils_AT.py:319): returns F.normalize(features); the following ``backward`` differentiates through it."""
         self.enable_training()
+        self.stash_ticket += 1
         if bool(normalize) != getattr(self, "_normalize_fare", False):
             self.set_option("normalize_fare", int(bool(normalize)))
             self._normalize_fare = bool(normalize)
@@ -820,6 +823,54 @@ class LeafCLIPText:
                                                     _ptr(self._buf["stash"]), _ptr(self.grads), _ptr(loss), _ptr(ws),
                                                     ws.numel(), self._stream()), "leaf_textfare_backward")
         return loss
+
+    def backward_from(self, feat: torch.Tensor, dfeat: torch.Tensor, accum_scale: float = 1.0, param_grads: bool = True,
+                      want_input_grad: bool = False, layer_events=None, ticket: Optional[int] = None):
+        """Backward from ANY upstream gradient through the stash of the last ``forward_train`` (leaf_text_backward): ``dfeat``
+        [n, embed_dim] = d loss / d ``feat`` of a loss the caller computed; ``accum_scale * dfeat`` is back-propagated, through
+        F.normalize as well when that forward ran with ``normalize=True``.  ``param_grads``: ACCUMULATE the parameter gradients into
+        ``self.grads`` (as ``backward``); ``want_input_grad``: also return the gradient with respect to the token embeddings
+        (= ``delta``), fp32 [rows, width] in the packed row layout of ``input_grad``.  Returns that tensor, or None when it was not
+        asked for.  ``layer_events``: as in ``backward``.  ``ticket``: the value of ``self.stash_ticket`` right after the forward
+        this gradient belongs to; when another ``forward_train`` has run since, the stash holds ITS activations and this raises
+        ``RuntimeError`` instead of differentiating through them."""
+        if ticket is not None and ticket != self.stash_ticket:
+            raise RuntimeError(f"backward_from: stale stash ticket {ticket} (current {self.stash_ticket}): another forward_train has "
+                               "overwritten the activations of this forward; one differentiable forward may be pending per model")
+        if not param_grads and not want_input_grad:
+            raise ValueError("backward_from: nothing to compute (param_grads and want_input_grad are both off)")
+        t = self._train_tokens
+        n = t.shape[0]
+        lens_p, cu, keep = self._train_plan
+        if tuple(feat.shape) != (n, self.cfg.embed_dim) or tuple(dfeat.shape) != (n, self.cfg.embed_dim):
+            raise ValueError(f"feat and dfeat must be [{n}, {self.cfg.embed_dim}]")
+        feat = feat.detach().to(device=self.device, dtype=torch.float32).contiguous()
+        dfeat = dfeat.detach().to(device=self.device, dtype=torch.float32).contiguous()
+        g = None
+        if want_input_grad:
+            rows = int(keep.sum()) if keep is not None else n * self.cfg.context_length
+            g = torch.empty(rows, self.cfg.width, dtype=torch.float32, device=self.device)
+        evs = None
+        if layer_events is not None:
+            if len(layer_events) != self.cfg.layers + 1:
+                raise ValueError(f"layer_events must hold {self.cfg.layers + 1} events")
+            evs = (C.c_void_p * len(layer_events))(*[C.c_void_p(e.cuda_event) for e in layer_events])
+        ws = self._workspace(2, n)
+        _lib.check(self._lib.leaf_text_backward(self._h, _ptr(self.flat), _ptr(self.w16_bwd), _ptr(t), lens_p, _ptr(cu), n, _ptr(feat),
+                                                _ptr(dfeat), float(accum_scale), _ptr(self._buf["stash"]),
+                                                _ptr(self.grads if param_grads else None), _ptr(g), _ptr(ws), ws.numel(),
+                                                self._stream(), evs), "leaf_text_backward")
+        return g
+
+    def encode_text_train(self, text, seq_lens=None, delta: Optional[torch.Tensor] = None, normalize: bool = False,
+                          pool_last: bool = False) -> torch.Tensor:
+        """``forward_train`` under autograd (leaf_amd/autograd.py): the returned features carry a ``grad_fn``, and ``backward()`` of any
+        PyTorch loss of them runs the engine's backward (``backward_from``).  Parameter gradients are ACCUMULATED into ``self.grads``,
+        the flat buffer that ``adamw_step`` / ``LeafAdamW`` consume -- NOT into ``.grad`` attributes; ``delta.grad`` is filled when
+        ``delta.requires_grad``.  One differentiable forward may be pending per model (a later ``forward_train`` makes the backward of
+        an earlier one raise).  Under ``torch.no_grad()`` this is ``forward_train``."""
+        from .autograd import encode_text_train
+        return encode_text_train(self, text, seq_lens=seq_lens, delta=delta, normalize=normalize, pool_last=pool_last)
 
     def clip_grads_(self, max_norm: Optional[float], pre_scale: float = 1.0) -> torch.Tensor:
         """``torch.nn.utils.clip_grad_norm_`` on the accumulated gradient buffer, in place (utils_AT.py:348-357 with

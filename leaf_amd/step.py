@@ -281,15 +281,32 @@ class GradReducer:
             self._cap_ev.record(self.comm)
         self._cap_pending = True
 
-    def backward(self, feat, anchor, accum_scale: float = 1.0, last_micro: bool = True):
-        """model.backward + (on the last micro-batch of an optimizer step) the bucketed reduction queued behind it."""
+    def _loss_backward(self, loss_fn, feat, anchor, accum_scale, events=None):
+        """A caller's loss instead of the fused TextFARE head: ``loss_fn(anchor, feat) -> 0-d tensor`` under autograd, ``feat`` from
+        ``encode_text_train``; back-propagates loss * accum_scale through the engine (leaf_amd/autograd.py), the block events of the
+        overlapped reduction handed to that backward.  Returns the detached loss."""
+        from .autograd import layer_events
+        loss = loss_fn(anchor, feat)
+        with layer_events(self.model, events):
+            (loss * accum_scale).backward()
+        return loss.detach()
+
+    def backward(self, feat, anchor, accum_scale: float = 1.0, last_micro: bool = True, loss_fn=None):
+        """model.backward + (on the last micro-batch of an optimizer step) the bucketed reduction queued behind it.  ``loss_fn``
+        (optional): a caller's loss of (anchor, feat) in place of TextFARE (``_loss_backward``); everything behind the backward --
+        bucketed or flat reduction, ``MicroClip`` -- is the same."""
         import torch.distributed as dist
         m = self.model
         if not (_dp_active() and self.overlap and last_micro):
+            if loss_fn is not None:
+                return self._loss_backward(loss_fn, feat, anchor, accum_scale)
             return m.backward(feat, anchor, accum_scale=accum_scale)
         if self.events is None:
             self._setup()
-        loss = m.backward(feat, anchor, accum_scale=accum_scale, layer_events=self.events)
+        if loss_fn is not None:
+            loss = self._loss_backward(loss_fn, feat, anchor, accum_scale, self.events)
+        else:
+            loss = m.backward(feat, anchor, accum_scale=accum_scale, layer_events=self.events)
         sparse = self.sparse_embed and getattr(self, "_cap_pending", False) and accum_scale == 1.0
         for ev_idx, ranges in self.plan:
             self.comm.wait_event(self.events[ev_idx])

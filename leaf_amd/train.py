@@ -2,8 +2,10 @@
 
 Mirrors the reference's host orchestration around the hot path:
 
-* ``train_one_epoch_text_only``  utils_AT.py:262-426 (same argument list; ``loss`` and ``scaler`` are accepted and
-  unused -- the reference never uses ``loss`` either; the fp16 gradient path carries its own device-side power-of-two loss scale)
+* ``train_one_epoch_text_only``  utils_AT.py:262-426 (same argument list; ``scaler`` is accepted and unused: the fp16 gradient
+  path carries its own device-side power-of-two loss scale.  ``loss=None``, what the entry script passes, is the fused TextFARE
+  head -- the reference never uses its ``loss`` argument either; a callable ``loss(text_features_frozen, text_features_adv) ->
+  0-d tensor`` replaces TextFARE by any PyTorch loss, back-propagated through the engine by leaf_amd/autograd.py)
 * ``cosine_lr`` / ``const_lr``   src/open_clip_train/scheduler.py:4-53
 * ``LeafAdamW``                  torch.optim.AdamW with the two groups of train_AT_text_only.py:323-341, executed
   by ONE fused HIP kernel over the flat parameter buffer after ONE flat RCCL all-reduce
@@ -418,14 +420,14 @@ class MicroClip:
                                "with --accum-freq > 1 under --precision amp: the reference un-scales the gradients once per "
                                "micro-batch, utils_AT.py:348-351, which torch.cuda.amp.GradScaler refuses; use amp_bf16)")
 
-    def backward(self, feat, anchor, micro: int):
+    def backward(self, feat, anchor, micro: int, loss_fn=None):
         from .step import _dp_active
         import torch.distributed as dist
         red = get_reducer(self.model)
         world = dist.get_world_size() if _dp_active() else 1
         if world > 1 and micro > 0:
             self.model.clip_grads_(None, pre_scale=1.0 / world)
-        loss = red.backward(feat, anchor, accum_scale=1.0 / (self.accum * world), last_micro=True)
+        loss = red.backward(feat, anchor, accum_scale=1.0 / (self.accum * world), last_micro=True, loss_fn=loss_fn)
         if world > 1:
             red.finish()
         self.model.clip_grads_(self.max_norm)
@@ -439,6 +441,8 @@ def train_one_epoch_text_only(model, model_frozen, tokenizer, V, data, loss, epo
     if getattr(args, "horovod", False):
         raise NotImplementedError("horovod is not supported; launch with torch.distributed.run (RCCL)")
     normalize_fare = bool(getattr(args, "normalize_fare", False))   # utils_AT.py:296,319
+    if loss is not None and not callable(loss):
+        raise TypeError("loss: None (the fused TextFARE head) or a callable loss(text_features_frozen, text_features_adv) -> 0-d tensor")
     MicroClip.check(args, scaler)
     micro_clip = MicroClip(model, args)
     device = torch.device(args.device)
@@ -505,13 +509,17 @@ def train_one_epoch_text_only(model, model_frozen, tokenizer, V, data, loss, epo
             # (opt-in sparse reduction of the token-embedding gradient, LEAF_DP_SPARSE_EMBED=1: this rank's token count travels now;
             # a no-op otherwise -- leaf_amd/step.py:GradReducer.begin_step)
             get_reducer(model).begin_step(int(np.count_nonzero(np.asarray(adv_tokens))))
-        feat = model.forward_train(adv_tokens, normalize=normalize_fare)
+        if loss is not None:
+            # a caller's loss: the same forward with a grad_fn; the reducer evaluates the loss and back-propagates it through the engine
+            feat = unwrap_model(model).encode_text_train(adv_tokens, normalize=normalize_fare)
+        else:
+            feat = model.forward_train(adv_tokens, normalize=normalize_fare)
         data_time_m.update(time.time() - end)
         if micro_clip.active:
-            loss_fare = micro_clip.backward(feat, anchor, i % args.accum_freq)                # device scalar, no sync
+            loss_fare = micro_clip.backward(feat, anchor, i % args.accum_freq, loss_fn=loss)  # device scalar, no sync
         else:
             loss_fare = get_reducer(model).backward(feat, anchor, accum_scale=1.0 / args.accum_freq,
-                                                    last_micro=(i + 1) % args.accum_freq == 0)
+                                                    last_micro=(i + 1) % args.accum_freq == 0, loss_fn=loss)
         for key in ("loss", "loss_FARE_text"):
             losses_accum[key] = losses_accum.get(key, 0) + loss_fare / args.accum_freq
         if (i + 1) % args.accum_freq == 0:
