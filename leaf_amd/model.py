@@ -91,6 +91,45 @@ def _lens_cu(lens):
     return lens, cu
 
 
+class _RowPlan:
+    """Row layout of one pass.  EOT trimming: the host ``lens`` (int32 [n], kept rows per sequence) and, once ``place``d, the device
+    ``cu`` (int32 [n + 1], rows in front of each sequence); the dense layout: neither.  The plan owns both arrays, so the C arguments
+    ``lens_ptr`` / ``cu_ptr`` stay valid for as long as it is alive."""
+
+    def __init__(self, lens=None):
+        self.lens, self._cu_host = _lens_cu(lens) if lens is not None else (None, None)
+        self.cu = None
+
+    def place(self, device):
+        """``cu`` on the device (pinned + non_blocking: a pageable H2D copy would make the host wait for all queued GPU work)"""
+        if self.lens is not None:
+            self.cu = torch.from_numpy(self._cu_host).pin_memory().to(device, non_blocking=True)
+        return self
+
+    @property
+    def lens_ptr(self):
+        return C.c_void_p(self.lens.ctypes.data if self.lens is not None else 0)
+
+    @property
+    def cu_ptr(self):
+        return _ptr(self.cu)
+
+    def rows(self, n: int, ctx: int) -> int:
+        return int(self.lens.sum()) if self.lens is not None else n * ctx
+
+
+@dataclass(frozen=True)
+class _TrainPass:
+    """What a successful ``forward_train`` leaves for the backward heads: the stash holds the activations of exactly this pass."""
+    tokens: torch.Tensor      # int32 [n, ctx] on the device
+    plan: _RowPlan
+    n: int
+    rows: int                 # packed rows: the leading dimension of ``delta`` and of every d_embed
+    normalize: bool
+    pool_last: bool
+    ticket: int               # ``stash_ticket`` of this pass
+
+
 class _ScoreTarget:
     """What a scoring pass compares its candidates with, the Python side of ``ScoreTarget`` in leaf_amd/csrc/api.hip: one anchor row
     per caption under an objective, or (``class_feat`` given) a class matrix shared by all captions with a label per caption and the
@@ -193,16 +232,20 @@ class LeafCLIPText:
         # exact work skipping: compute only rows up to EOT (include/leaf_hip.h, "EOT trimming"); LEAF_PACK=0 disables
         self.trim_rows = os.environ.get("LEAF_PACK", "1") != "0"
         self.training = False
-        # training state (allocated on demand)
-        self.grads = self.exp_avg = self.exp_avg_sq = self.w16_bwd = None
+        self.precise_encode = False   # encode_text's default for ``precise``
+        self._vocab_inv = None        # nn_project's inverse row norms of the token table, per weight version
+        self.split_masks = ()
+        self._split_buf = None
+        # training state (allocated by enable_training)
+        self.grads = self.exp_avg = self.exp_avg_sq = self.w16_bwd = self._clip_ws = self._clipi_ws = None
+        self._scaler_attached = False
         self.opt_step = 0
-        self.stash_ticket = 0     # bumped by every forward_train: names the forward whose activations the stash holds (backward_from)
+        self.stash_ticket = 0     # bumped by every successful forward_train: names the forward whose activations the stash holds
+        self.train_pass: Optional[_TrainPass] = None      # that forward (None: the stash holds nothing a backward may read)
         self.rows_scored = 0      # packed rows handed to the scoring passes so far (host-side count; bench.py reports it per rank)
         if trainable:
             self.enable_training()
         # default arithmetic of the forward-only passes: LEAF_PRECISION=rowsafe (default) | fast
-        self.split_masks = ()
-        self._split_buf = None
         mode = os.environ.get("LEAF_PRECISION", PRECISION_DEFAULT)
         if mode not in PRECISION_MODES:
             raise ValueError(f"LEAF_PRECISION={mode}: one of {sorted(PRECISION_MODES)}")
@@ -221,7 +264,7 @@ class LeafCLIPText:
         """Engine switches (leaf_text_set_option): 'chunk', 'last_layer_trim', 'normalize_fare' (training forward / backward on normalised features),
         'compact_resid' (1 default: the residual stream of the forward-only passes as the 16-bit copy + an 8-bit remainder per
         element instead of fp32 rows; 0 = fp32 rows), 'single_edit' (set per pass by the ``single_edit=`` argument of the scoring calls)."""
-        if name == "ln_fold" and not value and getattr(self, "split_masks", ()):
+        if name == "ln_fold" and not value and self.split_masks:
             self.set_split_masks(())          # the split GEMMs exist in the LN-folded forward only: switching folding off switches them off
         _lib.check(self._lib.leaf_text_set_option(self._h, name.encode(), int(value)), "leaf_text_set_option")
         return self
@@ -358,7 +401,7 @@ class LeafCLIPText:
 
     @property
     def split_blocks(self) -> int:
-        return len(getattr(self, "split_masks", ()))
+        return len(self.split_masks)
 
     def set_precision(self, mode: str):
         """'rowsafe' (default) | 'fast' (no split GEMMs: the round-5 arithmetic) -- see ``set_split_masks``."""
@@ -371,26 +414,26 @@ class LeafCLIPText:
             vv = list(v[:self.cfg.layers - 1])
             while vv and vv[-1] == 0:
                 vv.pop()
-            if tuple(vv) == tuple(getattr(self, "split_masks", ())):
+            if tuple(vv) == tuple(self.split_masks):
                 return k
         return "masks" + "-".join(str(x) for x in self.split_masks)
 
     def arithmetic_tag(self):
         """What a K/V cache depends on besides the weights: a cache built under one setting must not be consumed under another
         (the bit-exact prefix reuse would silently break)."""
-        return (int(self._lib.leaf_text_get_option(self._h, b"compact_resid")), tuple(getattr(self, "split_masks", ())))
+        return (int(self._lib.leaf_text_get_option(self._h, b"compact_resid")), tuple(self.split_masks))
 
     def _split_pack(self):
-        masks = getattr(self, "split_masks", ())
+        masks = self.split_masks
         arr = (C.c_int32 * max(len(masks), 1))(*masks)
-        _lib.check(self._lib.leaf_text_split_pack_masks(self._h, _ptr(self.flat), arr, len(masks), _ptr(getattr(self, "_split_buf", None)),
+        _lib.check(self._lib.leaf_text_split_pack_masks(self._h, _ptr(self.flat), arr, len(masks), _ptr(self._split_buf),
                                                         self._stream()), "leaf_text_split_pack_masks")
 
     def copy_from(self, other: "LeafCLIPText"):
         """Weights AND arithmetic of ``other`` (split blocks / policy, residual-stream format): a frozen copy must embed like its source."""
         self.flat.copy_(other.flat)
-        if tuple(getattr(other, "split_masks", ())) != tuple(getattr(self, "split_masks", ())):
-            self.set_split_masks(getattr(other, "split_masks", ()))
+        if tuple(other.split_masks) != tuple(self.split_masks):
+            self.set_split_masks(other.split_masks)
         self.set_option("compact_resid", other.arithmetic_tag()[0])
         self.logit_scale = other.logit_scale.clone()
         self.extra_state = dict(other.extra_state)
@@ -402,7 +445,7 @@ class LeafCLIPText:
         """fp32 masters -> 16-bit MFMA operand copies (forward dtype; + transposed bf16 when training)."""
         _lib.check(self._lib.leaf_text_pack_weights(self._h, _ptr(self.flat), _ptr(self.w16), _ptr(self.w16_bwd),
                                                     self._stream()), "leaf_text_pack_weights")
-        if getattr(self, "split_masks", ()):
+        if self.split_masks:
             self._split_pack()
         self._packed = True
 
@@ -415,18 +458,15 @@ class LeafCLIPText:
             raise ValueError(f"tokens must be [N,{self.cfg.context_length}], got {tuple(t.shape)}")
         return t
 
-    def _row_plan(self, text, seq_lens):
-        """(host lens pointer, device cu tensor, keep-alive) for EOT trimming, or NULLs for the dense layout.
-        Lengths come from the caller (host array) or, for host-resident tokens, from argmax(tokens) + 1."""
-        if not self.trim_rows:
-            return C.c_void_p(0), None, None
-        if seq_lens is None:
-            if not isinstance(text, np.ndarray) and not (isinstance(text, torch.Tensor) and text.device.type == "cpu"):
-                return C.c_void_p(0), None, None       # device-resident tokens, lengths unknown on the host
+    def _row_plan(self, text, seq_lens, place: bool = True) -> _RowPlan:
+        """The row layout of a pass over ``text``: EOT trimming with lengths from the caller (host array) or, for host-resident tokens,
+        from argmax(tokens) + 1; the dense layout when trimming is off or the tokens live on the device (lengths unknown on the
+        host).  ``place=False`` leaves the device copy of ``cu`` to the caller (``_RowPlan.place``)."""
+        host = isinstance(text, np.ndarray) or (isinstance(text, torch.Tensor) and text.device.type == "cpu")
+        if self.trim_rows and seq_lens is None and host:
             seq_lens = _host_lens(text)
-        lens, cu = _lens_cu(seq_lens)
-        # pinned + non_blocking: a pageable H2D copy would make the host wait for all queued GPU work
-        return C.c_void_p(lens.ctypes.data), torch.from_numpy(cu).pin_memory().to(self.device, non_blocking=True), lens
+        plan = _RowPlan(seq_lens if self.trim_rows else None)
+        return plan.place(self.device) if place else plan
 
     def encode_text(self, text, normalize: bool = False, seq_lens=None, precise: Optional[bool] = None) -> torch.Tensor:
         """``precise`` (default: the model's ``precise_encode`` attribute, False): the fp32-grade forward of precise.hip -- fp32 stored
@@ -436,27 +476,21 @@ class LeafCLIPText:
         if len(text) == 0:      # an empty batch encodes to an empty [0, embed_dim] tensor, as the torch module's (model.py:269-284)
             return torch.empty(0, self.cfg.embed_dim, dtype=torch.float32, device=self.device)
         if precise is None:
-            precise = getattr(self, "precise_encode", False)
-        if precise:
-            lens_p, cu, keep = self._row_plan(text, seq_lens)
-            t = self._tokens(text)
-            n = t.shape[0]
-            out = torch.empty(n, self.cfg.embed_dim, dtype=torch.float32, device=self.device)
-            ws = self._grow(("ws", "precise"), self._lib.leaf_text_precise_workspace_bytes(self._h, n))
-            _lib.check(self._lib.leaf_text_forward_precise(self._h, _ptr(self.flat), _ptr(t), lens_p, _ptr(cu), n, _ptr(out),
-                                                           int(bool(normalize)), _ptr(ws), ws.numel(), self._stream()),
-                       "leaf_text_forward_precise")
-            return out
-        if not self._packed:
+            precise = self.precise_encode
+        if not precise and not self._packed:
             self.pack()
-        lens_p, cu, keep = self._row_plan(text, seq_lens)
+        plan = self._row_plan(text, seq_lens)
         t = self._tokens(text)
         n = t.shape[0]
         out = torch.empty(n, self.cfg.embed_dim, dtype=torch.float32, device=self.device)
-        ws = self._workspace(0, n)
-        _lib.check(self._lib.leaf_text_forward(self._h, _ptr(self.flat), _ptr(self.w16), _ptr(t), lens_p, _ptr(cu), n,
-                                               _ptr(out), int(bool(normalize)), _ptr(ws), ws.numel(), self._stream()),
-                   "leaf_text_forward")
+        if precise:     # the fp32 masters alone, a workspace of its own
+            entry, weights = "leaf_text_forward_precise", (_ptr(self.flat),)
+            ws = self._grow(("ws", "precise"), self._lib.leaf_text_precise_workspace_bytes(self._h, n))
+        else:
+            entry, weights = "leaf_text_forward", (_ptr(self.flat), _ptr(self.w16))
+            ws = self._workspace(0, n)
+        _lib.check(getattr(self._lib, entry)(self._h, *weights, _ptr(t), plan.lens_ptr, plan.cu_ptr, n, _ptr(out), int(bool(normalize)),
+                                             _ptr(ws), ws.numel(), self._stream()), entry)
         return out
 
     def encode_text_kv(self, text, seq_lens=None, want_features: bool = False, slot: int = 0):
@@ -466,19 +500,18 @@ class LeafCLIPText:
         groups of captions, leaf_amd/attacks.py)."""
         if not self._packed:
             self.pack()
-        lens, cu = _lens_cu(_host_lens(text) if seq_lens is None else seq_lens)
-        cu_dev = torch.from_numpy(cu).pin_memory().to(self.device, non_blocking=True)
+        plan = _RowPlan(_host_lens(text) if seq_lens is None else seq_lens).place(self.device)
         t = self._tokens(text)
         n = t.shape[0]
-        kvbuf = self._kv_buffer(slot, int(cu[-1]))
+        rows = plan.rows(n, self.cfg.context_length)
+        kvbuf = self._kv_buffer(slot, rows)
         out = torch.empty(n, self.cfg.embed_dim, dtype=torch.float32, device=self.device) if want_features else None
         ws = self._workspace(0, n)
-        _lib.check(self._lib.leaf_text_forward_kv(self._h, _ptr(self.flat), _ptr(self.w16), _ptr(t),
-                                                  C.c_void_p(lens.ctypes.data), _ptr(cu_dev), n, _ptr(out), 0,
-                                                  _ptr(kvbuf), kvbuf.numel(), _ptr(ws), ws.numel(), self._stream()),
+        _lib.check(self._lib.leaf_text_forward_kv(self._h, _ptr(self.flat), _ptr(self.w16), _ptr(t), plan.lens_ptr, plan.cu_ptr, n,
+                                                  _ptr(out), 0, _ptr(kvbuf), kvbuf.numel(), _ptr(ws), ws.numel(), self._stream()),
                    "leaf_text_forward_kv")
         # q0: layer 0 holds the captions' Q rows too (this pass writes whole q|k|v rows) -- what a single_edit pass reads
-        cache = {"kv": kvbuf, "base_cu": cu_dev, "base_rows": int(cu[-1]), "lens": lens, "n": n, "arith": self.arithmetic_tag(),
+        cache = {"kv": kvbuf, "base_cu": plan.cu, "base_rows": rows, "lens": plan.lens, "n": n, "arith": self.arithmetic_tag(),
                  "q0": True, "tokens": t}
         return (cache, out) if want_features else cache
 
@@ -509,7 +542,7 @@ class LeafCLIPText:
         """one pass over all kept rows of the B * rho candidates, scored against ``target``"""
         if not self._packed:
             self.pack()
-        lens_p, cu, keep = self._row_plan(tokens, seq_lens)
+        plan = self._row_plan(tokens, seq_lens)
         if isinstance(tokens, np.ndarray):
             tokens = torch.from_numpy(tokens)
         t = self._tokens(tokens.reshape(-1, tokens.shape[-1]))
@@ -518,8 +551,8 @@ class LeafCLIPText:
             raise ValueError(f"{t.shape[0]} candidate rows != B*rho = {B}*{rho}")
         args, ret = target.bind(rho, self.cfg.embed_dim, want_features, want_loss)
         ws = self._workspace(1, B * rho)
-        self.rows_scored += int(keep.sum()) if keep is not None else B * rho * self.cfg.context_length
-        _lib.check(getattr(self._lib, target.dense)(self._h, _ptr(self.flat), _ptr(self.w16), _ptr(t), lens_p, _ptr(cu), *args,
+        self.rows_scored += plan.rows(B * rho, self.cfg.context_length)
+        _lib.check(getattr(self._lib, target.dense)(self._h, _ptr(self.flat), _ptr(self.w16), _ptr(t), plan.lens_ptr, plan.cu_ptr, *args,
                                                     _ptr(ws), ws.numel(), self._stream()), target.dense)
         return ret
 
@@ -677,6 +710,7 @@ class LeafCLIPText:
                 # gradient-scaler state + scratch of the guarded optimizer step (include/leaf_hip.h "gradient scaler"): attached to
                 # the handle, so the fp16 backward checks its 16-bit gradient tensors for saturation (LEAF_GRAD_SCALER=0 detaches)
                 self._clip_ws = torch.zeros(_lib.SC_WORDS + 2048, dtype=torch.float32, device=self.device)
+                self._clipi_ws = torch.zeros(2 + 2048, dtype=torch.float32, device=self.device)     # scratch of clip_grads_
             self._scaler_attached = os.environ.get("LEAF_GRAD_SCALER", "1") != "0"
             if self._scaler_attached:
                 _lib.check(self._lib.leaf_text_set_grad_scaler(self._h, _ptr(self._clip_ws)), "leaf_text_set_grad_scaler")
@@ -694,77 +728,79 @@ class LeafCLIPText:
         row a12): fp32 CUDA tensor [rows, width] in the PACKED row layout of this call (``rows_of(seq_lens)`` rows; dense
         [N * ctx, width] when rows are not trimmed), added to the token embeddings.  ``normalize`` = --normalize_fare
         (utils_AT.py:319): returns F.normalize(features); the following ``backward`` differentiates through it."""
+        # everything that can refuse the call comes before the first change of the model's training state
+        plan = self._row_plan(text, seq_lens, place=False)
+        rows = plan.rows(len(text), self.cfg.context_length)
+        if pool_last and (delta is not None or seq_lens is None or plan.lens is None):
+            raise ValueError("pool_last needs explicit seq_lens (and row trimming on) and takes no delta")
+        if delta is not None and (delta.dtype != torch.float32 or not delta.is_contiguous() or delta.numel() != rows * self.cfg.width):
+            raise ValueError(f"delta must be contiguous fp32 with {rows} x {self.cfg.width} elements")
         self.enable_training()
-        self.stash_ticket += 1
-        if bool(normalize) != getattr(self, "_normalize_fare", False):
-            self.set_option("normalize_fare", int(bool(normalize)))
-            self._normalize_fare = bool(normalize)
         if not self._packed:
             self.pack()
-        self._train_plan = self._row_plan(text, seq_lens)
-        lens_p, cu, keep = self._train_plan
+        plan.place(self.device)
         t = self._tokens(text)
         n = t.shape[0]
+        self.train_pass = None      # from here on the stash no longer holds the previous pass
         stash = self._grow("stash", self._lib.leaf_text_stash_bytes(self._h, n))
         out = torch.empty(n, self.cfg.embed_dim, dtype=torch.float32, device=self.device)
         ws = self._workspace(2, n)
-        if pool_last:
-            if delta is not None or seq_lens is None or keep is None:
-                raise ValueError("pool_last needs explicit seq_lens (and row trimming on) and takes no delta")
-            _lib.check(self._lib.leaf_text_forward_train_last(self._h, _ptr(self.flat), _ptr(self.w16), _ptr(t), lens_p, _ptr(cu), n,
-                                                              _ptr(out), _ptr(stash), stash.numel(), _ptr(ws), ws.numel(),
-                                                              self._stream()), "leaf_text_forward_train_last")
-            self._train_tokens = t
-            return out
-        if delta is not None:
-            rows = int(keep.sum()) if keep is not None else n * self.cfg.context_length
-            if delta.dtype != torch.float32 or not delta.is_contiguous() or delta.numel() != rows * self.cfg.width:
-                raise ValueError(f"delta must be contiguous fp32 with {rows} x {self.cfg.width} elements")
-        _lib.check(self._lib.leaf_text_forward_train_delta(self._h, _ptr(self.flat), _ptr(self.w16), _ptr(t), lens_p,
-                                                           _ptr(cu), n, _ptr(delta), _ptr(out), _ptr(stash),
-                                                           stash.numel(), _ptr(ws), ws.numel(), self._stream()),
-                   "leaf_text_forward_train_delta")
-        self._train_tokens = t
+        if self._lib.leaf_text_get_option(self._h, b"normalize_fare") != int(bool(normalize)):
+            self.set_option("normalize_fare", int(bool(normalize)))
+        entry, extra = ("leaf_text_forward_train_last", ()) if pool_last else ("leaf_text_forward_train_delta", (_ptr(delta),))
+        _lib.check(getattr(self._lib, entry)(self._h, _ptr(self.flat), _ptr(self.w16), _ptr(t), plan.lens_ptr, plan.cu_ptr, n, *extra,
+                                             _ptr(out), _ptr(stash), stash.numel(), _ptr(ws), ws.numel(), self._stream()), entry)
+        self.stash_ticket += 1
+        self.train_pass = _TrainPass(t, plan, n, rows, bool(normalize), bool(pool_last), self.stash_ticket)
         return out
+
+    def _last_pass(self, who: str, ticket: Optional[int] = None) -> _TrainPass:
+        """the pass whose activations the stash holds, for ``who``; ``ticket`` (optional): the ``stash_ticket`` it must carry"""
+        p = self.train_pass
+        if p is None:
+            raise RuntimeError(f"{who}: the stash holds no training pass; run forward_train first")
+        if ticket is not None and ticket != p.ticket:
+            raise RuntimeError(f"{who}: stale stash ticket {ticket} (current {p.ticket}): another forward_train has "
+                               "overwritten the activations of this forward; one differentiable forward may be pending per model")
+        return p
+
+    def _backward_call(self, p: _TrainPass, entry: str, feat: torch.Tensor, head, outs, d_embed: bool = False, events=None):
+        """The backward through the stash of pass ``p`` under one loss head.  Every C ``entry`` takes the shared arguments (handle, weights,
+        tokens, row plan, n, feat), the head's own values ``head``, the stash, its outputs ``outs(g)`` (tensors or None in the entry's
+        order; ``g``: the gradient of the token embeddings, fp32 [rows, width] packed, allocated here when ``d_embed``), workspace and
+        stream; an entry that takes block events gets ``events`` = (the caller's ``layer_events``,) behind them.  Returns ``g``."""
+        g = torch.empty(p.rows, self.cfg.width, dtype=torch.float32, device=self.device) if d_embed else None
+        if events is not None and events[0] is not None:
+            if len(events[0]) != self.cfg.layers + 1:
+                raise ValueError(f"layer_events must hold {self.cfg.layers + 1} events")
+            events = ((C.c_void_p * len(events[0]))(*[C.c_void_p(e.cuda_event) for e in events[0]]),)
+        ws = self._workspace(2, p.n)
+        _lib.check(getattr(self._lib, entry)(self._h, _ptr(self.flat), _ptr(self.w16_bwd), _ptr(p.tokens), p.plan.lens_ptr, p.plan.cu_ptr,
+                                             p.n, _ptr(feat), *head, _ptr(self._buf["stash"]), *map(_ptr, outs(g)), _ptr(ws), ws.numel(),
+                                             self._stream(), *(events or ())), entry)
+        return g
 
     def input_grad(self, feat: torch.Tensor, anchor: torch.Tensor):
         """TextFARE loss of (anchor, feat) and its gradient with respect to the token embeddings (= the gradient of
         ``delta``) through the stash of the last ``forward_train``: (loss 0-d, d_embed fp32 [rows, width] packed).
         No parameter gradient is touched (the inner step of the optional embedding-space PGD mode)."""
-        t = self._train_tokens
-        n = t.shape[0]
-        lens_p, cu, keep = self._train_plan
-        rows = int(keep.sum()) if keep is not None else n * self.cfg.context_length
+        p = self._last_pass("input_grad")
         loss = torch.empty((), dtype=torch.float32, device=self.device)
-        g = torch.empty(rows, self.cfg.width, dtype=torch.float32, device=self.device)
         anchor = anchor.to(device=self.device, dtype=torch.float32).contiguous()
-        ws = self._workspace(2, n)
-        _lib.check(self._lib.leaf_textfare_input_grad(self._h, _ptr(self.flat), _ptr(self.w16_bwd), _ptr(t), lens_p,
-                                                      _ptr(cu), n, _ptr(feat.contiguous()), _ptr(anchor),
-                                                      _ptr(self._buf["stash"]), _ptr(g), _ptr(loss), _ptr(ws), ws.numel(),
-                                                      self._stream()), "leaf_textfare_input_grad")
-        return loss, g
+        return loss, self._backward_call(p, "leaf_textfare_input_grad", feat.contiguous(), (_ptr(anchor),), lambda g: (g, loss), d_embed=True)
 
     def cosine_input_grad(self, feat: torch.Tensor, target: torch.Tensor, loss_weight: float = 1.0):
         """Cosine head of text embedding inversion on the stash of the last ``forward_train``: per sequence b the loss
         ``loss_weight (1 - cos(feat_b, target_b))`` and the gradient of the SUM over b with respect to the token embeddings, so
         every sequence gets the gradient of its own loss (src/pez/optim_utils.py:191-196 for one prompt and one target).
         Returns (cos fp32 [n], d_embed fp32 [rows, width] packed)."""
-        t = self._train_tokens
-        n = t.shape[0]
-        lens_p, cu, keep = self._train_plan
-        rows = int(keep.sum()) if keep is not None else n * self.cfg.context_length
+        p = self._last_pass("cosine_input_grad")
         target = target.to(device=self.device, dtype=torch.float32).contiguous()
-        if tuple(target.shape) != (n, self.cfg.embed_dim) or tuple(feat.shape) != (n, self.cfg.embed_dim):
-            raise ValueError(f"feat and target must be [{n}, {self.cfg.embed_dim}]")
-        cos = torch.empty(n, dtype=torch.float32, device=self.device)
-        g = torch.empty(rows, self.cfg.width, dtype=torch.float32, device=self.device)
-        ws = self._workspace(2, n)
-        _lib.check(self._lib.leaf_cosine_input_grad(self._h, _ptr(self.flat), _ptr(self.w16_bwd), _ptr(t), lens_p, _ptr(cu), n,
-                                                    _ptr(feat.contiguous()), _ptr(target), float(loss_weight),
-                                                    _ptr(self._buf["stash"]), _ptr(g), _ptr(cos), _ptr(ws), ws.numel(),
-                                                    self._stream()), "leaf_cosine_input_grad")
-        return cos, g
+        if tuple(target.shape) != (p.n, self.cfg.embed_dim) or tuple(feat.shape) != (p.n, self.cfg.embed_dim):
+            raise ValueError(f"feat and target must be [{p.n}, {self.cfg.embed_dim}]")
+        cos = torch.empty(p.n, dtype=torch.float32, device=self.device)
+        return cos, self._backward_call(p, "leaf_cosine_input_grad", feat.contiguous(), (_ptr(target), float(loss_weight)),
+                                        lambda g: (g, cos), d_embed=True)
 
     def nn_project(self, embeds: torch.Tensor):
         """PEZ's projection step (nn_project, src/pez/optim_utils.py:26-55): for every row of ``embeds`` [M, width] the id of the
@@ -777,7 +813,7 @@ class LeafCLIPText:
         q = embeds.contiguous()
         M = q.shape[0]
         table = self.params["token_embedding.weight"]
-        if getattr(self, "_vocab_inv", None) is None:
+        if self._vocab_inv is None:
             inv = torch.empty(V, dtype=torch.float32, device=self.device)
             _lib.check(self._lib.leaf_vocab_inv_norms(_ptr(table), V, d, _ptr(inv), self._stream()), "leaf_vocab_inv_norms")
             self._vocab_inv = inv
@@ -791,11 +827,9 @@ class LeafCLIPText:
     def pgd_step(self, delta: torch.Tensor, grad: torch.Tensor, alpha: float, eps: float, norm: str = "linf"):
         """In-place fused update of the resident perturbation for the rows of the last ``forward_train``:
         'linf': clamp(delta + alpha sign(grad), -eps, eps); 'l2': per-sequence normalised step + L2-ball projection."""
-        lens_p, cu, keep = self._train_plan
-        n = self._train_tokens.shape[0]
-        _lib.check(self._lib.leaf_pgd_step(_ptr(delta), _ptr(grad), _ptr(cu), n, self.cfg.context_length, self.cfg.width,
-                                           float(alpha), float(eps), {"linf": 0, "l2": 2}[norm], self._stream()),
-                   "leaf_pgd_step")
+        p = self._last_pass("pgd_step")
+        _lib.check(self._lib.leaf_pgd_step(_ptr(delta), _ptr(grad), p.plan.cu_ptr, p.n, self.cfg.context_length, self.cfg.width,
+                                           float(alpha), float(eps), {"linf": 0, "l2": 2}[norm], self._stream()), "leaf_pgd_step")
         return delta
 
     def backward(self, feat: torch.Tensor, anchor: torch.Tensor, accum_scale: float = 1.0, layer_events=None) -> torch.Tensor:
@@ -803,25 +837,12 @@ class LeafCLIPText:
         Accumulates into ``self.grads``; returns the (unscaled) loss as a 0-d CUDA tensor.
         ``layer_events``: optional list of cfg.layers + 1 ``torch.cuda.Event`` (already created, i.e. recorded once): event l
         is recorded when every gradient of block l is final, the last one when everything is (gradient-bucket overlap)."""
-        t = self._train_tokens
-        n = t.shape[0]
+        p = self._last_pass("backward")
         loss = torch.empty((), dtype=torch.float32, device=self.device)
         anchor = anchor.to(device=self.device, dtype=torch.float32).contiguous()
-        ws = self._workspace(2, n)
-        lens_p, cu, keep = self._train_plan
-        if layer_events is not None:
-            if len(layer_events) != self.cfg.layers + 1:
-                raise ValueError(f"layer_events must hold {self.cfg.layers + 1} events")
-            evs = (C.c_void_p * len(layer_events))(*[C.c_void_p(e.cuda_event) for e in layer_events])
-            _lib.check(self._lib.leaf_textfare_backward_events(self._h, _ptr(self.flat), _ptr(self.w16_bwd), _ptr(t), lens_p,
-                                                               _ptr(cu), n, _ptr(feat.contiguous()), _ptr(anchor), float(accum_scale),
-                                                               _ptr(self._buf["stash"]), _ptr(self.grads), _ptr(loss), _ptr(ws),
-                                                               ws.numel(), self._stream(), evs), "leaf_textfare_backward_events")
-            return loss
-        _lib.check(self._lib.leaf_textfare_backward(self._h, _ptr(self.flat), _ptr(self.w16_bwd), _ptr(t), lens_p,
-                                                    _ptr(cu), n, _ptr(feat.contiguous()), _ptr(anchor), float(accum_scale),
-                                                    _ptr(self._buf["stash"]), _ptr(self.grads), _ptr(loss), _ptr(ws),
-                                                    ws.numel(), self._stream()), "leaf_textfare_backward")
+        # the _events entry with NULL events is leaf_textfare_backward
+        self._backward_call(p, "leaf_textfare_backward_events", feat.contiguous(), (_ptr(anchor), float(accum_scale)),
+                            lambda g: (self.grads, loss), events=(layer_events,))
         return loss
 
     def backward_from(self, feat: torch.Tensor, dfeat: torch.Tensor, accum_scale: float = 1.0, param_grads: bool = True,
@@ -834,33 +855,15 @@ class LeafCLIPText:
         asked for.  ``layer_events``: as in ``backward``.  ``ticket``: the value of ``self.stash_ticket`` right after the forward
         this gradient belongs to; when another ``forward_train`` has run since, the stash holds ITS activations and this raises
         ``RuntimeError`` instead of differentiating through them."""
-        if ticket is not None and ticket != self.stash_ticket:
-            raise RuntimeError(f"backward_from: stale stash ticket {ticket} (current {self.stash_ticket}): another forward_train has "
-                               "overwritten the activations of this forward; one differentiable forward may be pending per model")
+        p = self._last_pass("backward_from", ticket)
         if not param_grads and not want_input_grad:
             raise ValueError("backward_from: nothing to compute (param_grads and want_input_grad are both off)")
-        t = self._train_tokens
-        n = t.shape[0]
-        lens_p, cu, keep = self._train_plan
-        if tuple(feat.shape) != (n, self.cfg.embed_dim) or tuple(dfeat.shape) != (n, self.cfg.embed_dim):
-            raise ValueError(f"feat and dfeat must be [{n}, {self.cfg.embed_dim}]")
+        if tuple(feat.shape) != (p.n, self.cfg.embed_dim) or tuple(dfeat.shape) != (p.n, self.cfg.embed_dim):
+            raise ValueError(f"feat and dfeat must be [{p.n}, {self.cfg.embed_dim}]")
         feat = feat.detach().to(device=self.device, dtype=torch.float32).contiguous()
         dfeat = dfeat.detach().to(device=self.device, dtype=torch.float32).contiguous()
-        g = None
-        if want_input_grad:
-            rows = int(keep.sum()) if keep is not None else n * self.cfg.context_length
-            g = torch.empty(rows, self.cfg.width, dtype=torch.float32, device=self.device)
-        evs = None
-        if layer_events is not None:
-            if len(layer_events) != self.cfg.layers + 1:
-                raise ValueError(f"layer_events must hold {self.cfg.layers + 1} events")
-            evs = (C.c_void_p * len(layer_events))(*[C.c_void_p(e.cuda_event) for e in layer_events])
-        ws = self._workspace(2, n)
-        _lib.check(self._lib.leaf_text_backward(self._h, _ptr(self.flat), _ptr(self.w16_bwd), _ptr(t), lens_p, _ptr(cu), n, _ptr(feat),
-                                                _ptr(dfeat), float(accum_scale), _ptr(self._buf["stash"]),
-                                                _ptr(self.grads if param_grads else None), _ptr(g), _ptr(ws), ws.numel(),
-                                                self._stream(), evs), "leaf_text_backward")
-        return g
+        return self._backward_call(p, "leaf_text_backward", feat, (_ptr(dfeat), float(accum_scale)),
+                                   lambda g: (self.grads if param_grads else None, g), d_embed=want_input_grad, events=(layer_events,))
 
     def encode_text_train(self, text, seq_lens=None, delta: Optional[torch.Tensor] = None, normalize: bool = False,
                           pool_last: bool = False) -> torch.Tensor:
@@ -876,8 +879,6 @@ class LeafCLIPText:
         """``torch.nn.utils.clip_grad_norm_`` on the accumulated gradient buffer, in place (utils_AT.py:348-357 with
         --accum-freq > 1: the running sum is clipped after every micro-batch's backward).  ``pre_scale`` is applied in the same
         pass; ``max_norm=None`` only applies it.  Returns the 0-d norm tensor (of pre_scale * grads, before clipping)."""
-        if getattr(self, "_clipi_ws", None) is None:
-            self._clipi_ws = torch.zeros(2 + 2048, dtype=torch.float32, device=self.device)
         _lib.check(self._lib.leaf_clip_grads_inplace(_ptr(self.grads), self.n_params, float(pre_scale),
                                                      float(max_norm) if max_norm is not None else float("inf"),
                                                      _ptr(self._clipi_ws), self._stream()), "leaf_clip_grads_inplace")
@@ -897,10 +898,8 @@ class LeafCLIPText:
         self.opt_step += 1
         self._vocab_inv = None      # nn_project's table norms belong to the weights before this step
         # with the gradient scaler attached a saturated backward has poisoned the gradient with a NaN that only the guard stops
-        guard = guard or getattr(self, "_scaler_attached", False)
+        guard = guard or self._scaler_attached
         if max_norm is not None or guard:
-            if getattr(self, "_clip_ws", None) is None:
-                self._clip_ws = torch.zeros(_lib.SC_WORDS + 2048, dtype=torch.float32, device=self.device)
             _lib.check(self._lib.leaf_adamw_step_clip(_ptr(self.flat), _ptr(self.grads), _ptr(self.exp_avg),
                                                       _ptr(self.exp_avg_sq), self.n_params, self.n_decay, float(lr),
                                                       float(betas[0]), float(betas[1]), float(eps), float(weight_decay),
@@ -918,7 +917,7 @@ class LeafCLIPText:
 
     def skipped_steps(self) -> int:
         """Optimizer steps skipped by the non-finite guard so far (synchronises: call it where the loop already does)."""
-        ws = getattr(self, "_clip_ws", None)
+        ws = self._clip_ws
         return int(ws[_lib.SC_SKIPPED].item()) if ws is not None else 0
 
     def applied_steps(self) -> int:
@@ -928,7 +927,7 @@ class LeafCLIPText:
     def set_applied_steps(self, step: int):
         """After loading optimizer state: ``step`` applied steps so far, none skipped."""
         self.opt_step = int(step)
-        ws = getattr(self, "_clip_ws", None)
+        ws = self._clip_ws
         if ws is not None:
             ws[_lib.SC_SKIPPED] = 0.0
             ws[_lib.SC_APPLIED] = float(step)
@@ -936,7 +935,7 @@ class LeafCLIPText:
     def grad_scaler_state(self) -> dict:
         """GradScaler-style bookkeeping of the fp16 gradient path (synchronises): the persistent loss-scale factor 2^backoff,
         steps skipped in all / because a 16-bit gradient tensor saturated."""
-        ws = getattr(self, "_clip_ws", None)
+        ws = self._clip_ws
         if ws is None:
             return {"loss_scale_factor": 1.0, "skipped": 0, "skipped_saturated": 0}
         h = ws[:_lib.SC_WORDS].cpu()

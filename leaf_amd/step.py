@@ -318,7 +318,7 @@ class GradReducer:
                     self._cap_ev.synchronize()
                     self._cap_pending = False
                     cap = dist.get_world_size() * (int(self._cap_host[0]) + 1)
-                    reduce_token_rows(m.grads[off_t:off_t + n_t].view(shape_t), m._train_tokens, cap)
+                    reduce_token_rows(m.grads[off_t:off_t + n_t].view(shape_t), m.train_pass.tokens, cap)
                     ranges = [(o, c) for (o, c) in _minus(ranges, off_t, n_t)]
                 for off, numel in ranges:
                     if numel:

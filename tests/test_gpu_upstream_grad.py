@@ -22,6 +22,7 @@ pytestmark = pytest.mark.gpu
 SOT, EOT = 49406, 49407
 TINY_LENS = [2, 5, 77, 9, 16, 17, 33, 3]            # ragged, a length-2 caption (SOT, EOT) and a full row
 VITL_LENS = [3, 11, 17, 32, 40]
+PASS_LENS = [2, 5, 77]                               # the length set of tests/test_gpu_train_pass.py: shortest legal row, mid row, full context
 
 
 @pytest.fixture(scope="module")
@@ -136,7 +137,8 @@ def _anchor(env, m, toks, normalize, seed):
 @pytest.mark.parametrize("accum", [1.0, 0.5])
 @pytest.mark.parametrize("normalize", [False, True])
 @pytest.mark.parametrize("packed", [True, False])
-@pytest.mark.parametrize("name,lens", [("tiny-test", TINY_LENS), ("tiny-test-quickgelu", TINY_LENS), ("ViT-L-14", VITL_LENS)])
+@pytest.mark.parametrize("name,lens", [("tiny-test", TINY_LENS), ("tiny-test-quickgelu", TINY_LENS), ("ViT-L-14", VITL_LENS),
+                                       ("tiny-test", PASS_LENS)])
 def test_backward_from_equals_the_textfare_backward_bit_for_bit(env, models, name, lens, packed, normalize, accum):
     lib, torch, dev = env
     m = models(name)
