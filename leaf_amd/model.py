@@ -130,6 +130,22 @@ class _TrainPass:
     ticket: int               # ``stash_ticket`` of this pass
 
 
+@dataclass(frozen=True, slots=True)
+class _KvCache:
+    """The clean captions' per-layer q|k|v rows in one of the model's cache buffers, as ``encode_text_kv`` or ``score_candidates_fused``
+    left them.  A later writer of the same slot rewrites those bytes: the cache is then stale, and a pass over it is refused."""
+    buf: torch.Tensor         # the slot's byte buffer
+    base_cu: torch.Tensor     # int32 [n + 1] on the device: rows in front of each caption
+    base_rows: int
+    lens: np.ndarray          # host int32 [n]: rows per caption
+    n: int
+    arith: tuple              # ``arithmetic_tag()`` of the pass that wrote the rows
+    q0: bool                  # layer 0 holds the captions' Q rows too: what a single_edit pass reads
+    tokens: torch.Tensor      # int32 [n, ctx] on the device
+    slot: int
+    ticket: int               # ``kv_tickets[slot]`` of the pass that wrote the rows
+
+
 class _ScoreTarget:
     """What a scoring pass compares its candidates with, the Python side of ``ScoreTarget`` in leaf_amd/csrc/api.hip: one anchor row
     per caption under an objective, or (``class_feat`` given) a class matrix shared by all captions with a label per caption and the
@@ -138,10 +154,9 @@ class _ScoreTarget:
     def __init__(self, anchor=None, objective="l2", class_feat=None, labels=None, want_pred=False, want_logits=False):
         self.anchor, self.obj = anchor, _OBJ[objective]
         self.class_feat, self.labels, self.want_pred, self.want_logits = class_feat, labels, want_pred, want_logits
-        if class_feat is None:
-            self.B, self.dense, self.prefix = int(anchor.shape[0]), "leaf_score_candidates", "leaf_score_candidates_prefix"
-        else:
-            self.B, self.dense, self.prefix = int(labels.shape[0]), "leaf_score_candidates_cls", "leaf_score_candidates_prefix_cls"
+        self.B = int((anchor if class_feat is None else labels).shape[0])
+        self.dense, self.prefix = (("leaf_score_candidates", "leaf_score_candidates_prefix") if class_feat is None else
+                                   ("leaf_score_candidates_cls", "leaf_score_candidates_prefix_cls"))
 
     def bind(self, rho: int, embed_dim: int, want_features: bool, want_loss: bool):
         """Output buffers of one pass over B * rho candidates.  Returns (the C arguments from the target to the last output, which
@@ -161,6 +176,42 @@ class _ScoreTarget:
                 (idx, feat, (loss if want_loss else None), pred, logits))
 
 
+@dataclass(slots=True)
+class _ScorePlan:
+    """What ``score_candidates_prepare`` hands to ``score_candidates_run``: everything of a prefix-reuse pass but the prefix lengths.
+    The plan keeps alive every buffer whose address ``call`` holds."""
+    full: np.ndarray          # host int32 [n]: the candidates' full lengths
+    limit: np.ndarray         # ``_prefix_limit`` of them
+    host: torch.Tensor        # pinned int32 [cu (n + 1) | prefix (n)], staged for one host-to-device copy
+    tokens: torch.Tensor      # the candidates, int32 [n, ctx] on the device
+    rho: int
+    cache: _KvCache
+    single_edit: bool
+    target: _ScoreTarget
+    ws: torch.Tensor
+    ret: tuple                # what the scoring call returns
+    call: object              # the C call: (suffix lens, cu, prefix) -> None
+
+
+def _prefix_limit(full, base_lens, rho: int) -> np.ndarray:
+    """int32 [n]: the longest prefix candidate ``i`` (``full[i]`` rows) may take from the cache of caption ``i // rho`` -- its own EOT
+    row is always computed, and no more rows are read than the caption's cache holds"""
+    return np.minimum(np.asarray(full, dtype=np.int32) - 1, np.repeat(np.asarray(base_lens, dtype=np.int32), rho))
+
+
+def _clamp_prefix(prefix_lens, limit, out) -> np.ndarray:
+    """``prefix_lens`` clamped to ``limit`` (``_prefix_limit``) into the int32 array ``out``"""
+    return np.minimum(np.asarray(prefix_lens).reshape(-1), limit, out=out, casting="unsafe")
+
+
+def _check_equal_lengths(full, base_lens, rho: int) -> None:
+    """the length half of the ``single_edit`` promise: candidate ``i`` is as long as caption ``i // rho``"""
+    full, want = np.asarray(full).reshape(-1), np.repeat(np.asarray(base_lens).reshape(-1), rho)
+    if (full != want).any():
+        i = int((full != want).argmax())
+        raise ValueError(f"single_edit: candidate {i} has length {int(full[i])}, its caption {int(want[i])}")
+
+
 def verify_single_edit(cand_tokens, cand_lens, prefix, base_tokens, base_lens, rho: int) -> None:
     """The promise of a ``single_edit`` scoring pass, checked on the tokens (``LEAF_VERIFY_SINGLE_EDIT=1``; tests and debugging: the
     comparison needs the tokens on the host): candidate ``i`` belongs to caption ``i // rho``, has the caption's length, and differs
@@ -175,12 +226,8 @@ def verify_single_edit(cand_tokens, cand_lens, prefix, base_tokens, base_lens, r
     if n != base.shape[0] * rho:
         raise ValueError(f"single_edit: {n} candidates for {base.shape[0]} captions x rho = {rho}")
     cl = host(cand_lens).reshape(-1).astype(np.int64)
-    bl = np.repeat(host(base_lens).reshape(-1).astype(np.int64), rho)
     pfx = host(prefix).reshape(-1).astype(np.int64)
-    bad = np.nonzero(cl != bl)[0]
-    if bad.size:
-        i = int(bad[0])
-        raise ValueError(f"single_edit: candidate {i} has length {int(cl[i])}, its caption {int(bl[i])}")
+    _check_equal_lengths(cl, host(base_lens), rho)
     pos = np.arange(ctx)[None, :]
     differs = (cand != np.repeat(base, rho, axis=0)) & (pos < cl[:, None]) & (pos != pfx[:, None])
     bad = np.nonzero(differs.any(-1))[0]
@@ -242,6 +289,7 @@ class LeafCLIPText:
         self.opt_step = 0
         self.stash_ticket = 0     # bumped by every successful forward_train: names the forward whose activations the stash holds
         self.train_pass: Optional[_TrainPass] = None      # that forward (None: the stash holds nothing a backward may read)
+        self.kv_tickets: Dict[int, int] = {}      # per K/V cache slot: bumped by every pass that has rewritten the slot (_kv_cache)
         self.rows_scored = 0      # packed rows handed to the scoring passes so far (host-side count; bench.py reports it per rank)
         if trainable:
             self.enable_training()
@@ -269,10 +317,13 @@ class LeafCLIPText:
         _lib.check(self._lib.leaf_text_set_option(self._h, name.encode(), int(value)), "leaf_text_set_option")
         return self
 
-    def _single_edit_call(self, on: bool, fn):
-        """``fn()`` with the engine's per-pass ``single_edit`` option set for its duration."""
+    def _single_edit_call(self, on: bool, fn, promise):
+        """``fn()`` with the engine's per-pass ``single_edit`` option set for its duration.  ``promise``: the arguments of
+        ``verify_single_edit``, checked first under ``LEAF_VERIFY_SINGLE_EDIT=1``."""
         if not on:
             return fn()
+        if os.environ.get("LEAF_VERIFY_SINGLE_EDIT") == "1":
+            verify_single_edit(*promise)
         self.set_option("single_edit", 1)
         try:
             return fn()
@@ -420,8 +471,9 @@ class LeafCLIPText:
 
     def arithmetic_tag(self):
         """What a K/V cache depends on besides the weights: a cache built under one setting must not be consumed under another
-        (the bit-exact prefix reuse would silently break)."""
-        return (int(self._lib.leaf_text_get_option(self._h, b"compact_resid")), tuple(self.split_masks))
+        (the bit-exact prefix reuse would silently break): (compact_resid, split masks, ln_fold)."""
+        return (int(self._lib.leaf_text_get_option(self._h, b"compact_resid")), tuple(self.split_masks),
+                int(self._lib.leaf_text_get_option(self._h, b"ln_fold")))
 
     def _split_pack(self):
         masks = self.split_masks
@@ -440,6 +492,12 @@ class LeafCLIPText:
         self._packed = False
         self._vocab_inv = None
         return self
+
+    def _weights(self):
+        """the C arguments (fp32 masters, 16-bit operand copies) of a pass, the copies packed first when they are out of date"""
+        if not self._packed:
+            self.pack()
+        return _ptr(self.flat), _ptr(self.w16)
 
     def pack(self):
         """fp32 masters -> 16-bit MFMA operand copies (forward dtype; + transposed bf16 when training)."""
@@ -477,8 +535,6 @@ class LeafCLIPText:
             return torch.empty(0, self.cfg.embed_dim, dtype=torch.float32, device=self.device)
         if precise is None:
             precise = self.precise_encode
-        if not precise and not self._packed:
-            self.pack()
         plan = self._row_plan(text, seq_lens)
         t = self._tokens(text)
         n = t.shape[0]
@@ -487,7 +543,7 @@ class LeafCLIPText:
             entry, weights = "leaf_text_forward_precise", (_ptr(self.flat),)
             ws = self._grow(("ws", "precise"), self._lib.leaf_text_precise_workspace_bytes(self._h, n))
         else:
-            entry, weights = "leaf_text_forward", (_ptr(self.flat), _ptr(self.w16))
+            entry, weights = "leaf_text_forward", self._weights()
             ws = self._workspace(0, n)
         _lib.check(getattr(self._lib, entry)(self._h, *weights, _ptr(t), plan.lens_ptr, plan.cu_ptr, n, _ptr(out), int(bool(normalize)),
                                              _ptr(ws), ws.numel(), self._stream()), entry)
@@ -495,11 +551,9 @@ class LeafCLIPText:
 
     def encode_text_kv(self, text, seq_lens=None, want_features: bool = False, slot: int = 0):
         """Forward of the clean captions that keeps every layer's q|k|v rows for prefix reuse by the search
-        (include/leaf_hip.h, "prefix reuse").  Returns an opaque cache (and the features when asked).  ``slot``: which of the
+        (include/leaf_hip.h, "prefix reuse").  Returns the cache, a ``_KvCache`` (and the features when asked).  ``slot``: which of the
         model's cache buffers to fill -- caches of different slots can be alive at the same time (the string search pipelines
-        groups of captions, leaf_amd/attacks.py)."""
-        if not self._packed:
-            self.pack()
+        groups of captions, leaf_amd/attacks.py); filling a slot makes every earlier cache of that slot stale."""
         plan = _RowPlan(_host_lens(text) if seq_lens is None else seq_lens).place(self.device)
         t = self._tokens(text)
         n = t.shape[0]
@@ -507,13 +561,36 @@ class LeafCLIPText:
         kvbuf = self._kv_buffer(slot, rows)
         out = torch.empty(n, self.cfg.embed_dim, dtype=torch.float32, device=self.device) if want_features else None
         ws = self._workspace(0, n)
-        _lib.check(self._lib.leaf_text_forward_kv(self._h, _ptr(self.flat), _ptr(self.w16), _ptr(t), plan.lens_ptr, plan.cu_ptr, n,
+        _lib.check(self._lib.leaf_text_forward_kv(self._h, *self._weights(), _ptr(t), plan.lens_ptr, plan.cu_ptr, n,
                                                   _ptr(out), 0, _ptr(kvbuf), kvbuf.numel(), _ptr(ws), ws.numel(), self._stream()),
                    "leaf_text_forward_kv")
         # q0: layer 0 holds the captions' Q rows too (this pass writes whole q|k|v rows) -- what a single_edit pass reads
-        cache = {"kv": kvbuf, "base_cu": plan.cu, "base_rows": rows, "lens": plan.lens, "n": n, "arith": self.arithmetic_tag(),
-                 "q0": True, "tokens": t}
+        cache = self._kv_cache(kvbuf, plan.cu, rows, plan.lens, True, t, slot)
         return (cache, out) if want_features else cache
+
+    def _kv_cache(self, buf, base_cu, base_rows: int, lens, q0: bool, tokens, slot: int) -> _KvCache:
+        """The record of the rows that a C call, which has returned success, wrote into cache buffer ``slot``: the slot's ticket moves
+        on, so every earlier cache of the slot is stale from here."""
+        self.kv_tickets[slot] = ticket = self.kv_tickets.get(slot, 0) + 1
+        return _KvCache(buf, base_cu, base_rows, lens, int(tokens.shape[0]), self.arithmetic_tag(), q0, tokens, slot, ticket)
+
+    def _check_cache(self, cache: _KvCache, B: int, rho: int, full, single_edit: bool) -> None:
+        """Refuses a pass of B * rho candidates (lengths ``full``) over ``cache`` unless it holds the rows of B captions, written under
+        the arithmetic the model runs now and not rewritten since."""
+        if cache.n != B or full.size != B * rho:
+            raise ValueError("candidate rows / kv cache do not match B*rho")
+        if cache.arith != self.arithmetic_tag():
+            raise ValueError(f"K/V cache built under arithmetic {cache.arith} (compact_resid, split masks, ln_fold), "
+                             f"the model now runs {self.arithmetic_tag()}: rebuild the cache (encode_text_kv)")
+        if cache.ticket != self.kv_tickets.get(cache.slot):
+            raise RuntimeError(f"stale K/V cache: ticket {cache.ticket} of slot {cache.slot} (current {self.kv_tickets.get(cache.slot)}): the "
+                               "slot was rewritten since; rebuild the cache (encode_text_kv / score_candidates_fused)")
+        if single_edit:
+            # the pass reads the captions' Q rows of layer 0 and, behind the edit, as many cache rows as the candidate is long
+            if not cache.q0:
+                raise ValueError("single_edit pass on a K/V cache without the captions' layer-0 Q rows (written by a fused first stage "
+                                 "that did not run with single_edit): rebuild it with encode_text_kv or score_candidates_fused(single_edit=True)")
+            _check_equal_lengths(full, cache.lens, rho)
 
     def score_candidates(self, tokens, anchor: torch.Tensor, rho: int, objective: str = "l2", want_features=True,
                          want_loss=False, seq_lens=None, prefix_lens=None, kv=None, single_edit: bool = False):
@@ -530,95 +607,73 @@ class LeafCLIPText:
         token-level substitutions (``leaf_amd.step.search_synthetic``); NOT for the string search of ``leaf_amd.attacks`` /
         ``charmer``, where a character edit re-tokenises the rest of the caption.  ``LEAF_VERIFY_SINGLE_EDIT=1`` checks the promise
         against the tokens (a device-to-host copy)."""
-        if prefix_lens is not None and kv is not None and self.trim_rows:
-            return self.score_candidates_run(self.score_candidates_prepare(tokens, anchor, rho, objective, want_features, want_loss,
-                                                                           seq_lens=seq_lens, kv=kv, single_edit=single_edit), prefix_lens)
-        return self._score_dense(self._anchor_target(anchor, objective), tokens, rho, want_features, want_loss, seq_lens)
+        return self._score(self._anchor_target(anchor, objective), tokens, rho, want_features, want_loss, seq_lens, prefix_lens, kv, single_edit)
 
     def _anchor_target(self, anchor, objective):
         return _ScoreTarget(anchor.to(device=self.device, dtype=torch.float32).contiguous(), objective)
 
+    def _score(self, target, tokens, rho, want_features, want_loss, seq_lens, prefix_lens, kv, single_edit=False):
+        """one scoring pass against ``target``: prefix reuse when the caller gives prefix lengths and a cache, else all kept rows"""
+        if prefix_lens is not None and kv is not None and self.trim_rows:
+            return self.score_candidates_run(self._prepare(target, tokens, rho, want_features, want_loss, seq_lens, kv, single_edit), prefix_lens)
+        return self._score_dense(target, tokens, rho, want_features, want_loss, seq_lens)
+
+    def _candidates(self, tokens, B: int, rho: int = 1) -> torch.Tensor:
+        """the rho candidates of each of B captions ([B * rho, ctx] or [B, rho, ctx]; rho = 1: the captions themselves) on the device,
+        as int32 [B * rho, ctx]"""
+        t = self._tokens(tokens.reshape(-1, tokens.shape[-1]))
+        if t.shape[0] != B * rho:
+            raise ValueError(f"{t.shape[0]} token rows != B*rho = {B}*{rho}")
+        return t
+
     def _score_dense(self, target, tokens, rho, want_features, want_loss, seq_lens):
         """one pass over all kept rows of the B * rho candidates, scored against ``target``"""
-        if not self._packed:
-            self.pack()
         plan = self._row_plan(tokens, seq_lens)
-        if isinstance(tokens, np.ndarray):
-            tokens = torch.from_numpy(tokens)
-        t = self._tokens(tokens.reshape(-1, tokens.shape[-1]))
-        B = target.B
-        if t.shape[0] != B * rho:
-            raise ValueError(f"{t.shape[0]} candidate rows != B*rho = {B}*{rho}")
+        t = self._candidates(tokens, target.B, rho)
         args, ret = target.bind(rho, self.cfg.embed_dim, want_features, want_loss)
-        ws = self._workspace(1, B * rho)
-        self.rows_scored += plan.rows(B * rho, self.cfg.context_length)
-        _lib.check(getattr(self._lib, target.dense)(self._h, _ptr(self.flat), _ptr(self.w16), _ptr(t), plan.lens_ptr, plan.cu_ptr, *args,
+        ws = self._workspace(1, t.shape[0])
+        self.rows_scored += plan.rows(t.shape[0], self.cfg.context_length)
+        _lib.check(getattr(self._lib, target.dense)(self._h, *self._weights(), _ptr(t), plan.lens_ptr, plan.cu_ptr, *args,
                                                     _ptr(ws), ws.numel(), self._stream()), target.dense)
         return ret
 
     def score_candidates_prepare(self, tokens, anchor, rho, objective="l2", want_features=True, want_loss=False, seq_lens=None, kv=None,
-                                 single_edit: bool = False, cls=None):
-        """Everything of a prefix-reuse ``score_candidates`` call that does NOT depend on the prefix lengths: token / anchor placement,
-        output buffers, the length limits, a pinned staging buffer for the row plan, the C entry and its arguments known by now.  The
-        search calls this BEFORE it waits for the previous stage's winners and ``score_candidates_run(plan, prefix_lens)`` right after
-        them: the device idles at that boundary for as long as the host needs between the two (round 4, tools/stage_hole_probe.py:
-        270 -> 94 us at ViT-L B = 128, 181 -> 123 us at ViT-H B = 32).  ``cls`` (from ``_cls_target``; ``anchor`` is then None): score against a class matrix, ``score_candidates_cls``."""
-        if not self._packed:
-            self.pack()
-        target = cls if cls is not None else self._anchor_target(anchor, objective)
-        if seq_lens is None:
-            seq_lens = _host_lens(tokens)
-        full = np.ascontiguousarray(np.asarray(seq_lens).reshape(-1), dtype=np.int32)
-        n = full.size
-        # prefix <= full - 1 (keep at least the EOT row) and <= the rows the cache really holds
-        limit = np.minimum(full - 1, np.repeat(kv["lens"].astype(np.int32), rho))
-        host = torch.empty(2 * n + 1, dtype=torch.int32, pin_memory=True)      # [cu (n + 1) | prefix (n)]
-        if isinstance(tokens, np.ndarray):
-            tokens = torch.from_numpy(tokens)
-        t = self._tokens(tokens.reshape(-1, tokens.shape[-1]))
-        B = target.B
-        if t.shape[0] != B * rho or kv["n"] != B or n != B * rho:
-            raise ValueError("candidate rows / kv cache do not match B*rho")
-        if kv.get("arith", self.arithmetic_tag()) != self.arithmetic_tag():
-            raise ValueError(f"K/V cache built under arithmetic {kv['arith']} (compact_resid, split masks), "
-                             f"the model now runs {self.arithmetic_tag()}: rebuild the cache (encode_text_kv)")
-        if single_edit:
-            # the pass reads the captions' Q rows of layer 0 and, behind the edit, as many cache rows as the candidate is long
-            if not kv.get("q0"):
-                raise ValueError("single_edit pass on a K/V cache without the captions' layer-0 Q rows (written by a fused first stage "
-                                 "that did not run with single_edit): rebuild it with encode_text_kv or score_candidates_fused(single_edit=True)")
-            if not np.array_equal(full, np.repeat(kv["lens"].astype(np.int32), rho)):
-                raise ValueError("single_edit pass: a candidate's length differs from its caption's")
-        args, ret = target.bind(rho, self.cfg.embed_dim, want_features, want_loss)
-        ws = self._workspace(1, B * rho)
-        # head / tail: the C arguments in front of and behind the three that ``score_candidates_run`` computes
-        return {"full": full, "limit": limit, "host": host, "t": t, "rho": rho, "kv": kv, "single_edit": bool(single_edit),
-                "target": target, "ws": ws, "entry": target.prefix, "fn": getattr(self._lib, target.prefix),
-                "head": (self._h, _ptr(self.flat), _ptr(self.w16), _ptr(t)),
-                "tail": (_ptr(kv["base_cu"]), _ptr(kv["kv"]), kv["base_rows"], int(full.max()), *args, _ptr(ws), ws.numel()),
-                "ret": ret}
+                                 single_edit: bool = False) -> _ScorePlan:
+        """Everything of a prefix-reuse ``score_candidates`` call that does NOT depend on the prefix lengths: the check of the cache,
+        token / anchor placement, output buffers, the length limits, a pinned staging buffer for the row plan, the C call with its
+        arguments known by now.  The search calls this BEFORE it waits for the previous stage's winners and
+        ``score_candidates_run(plan, prefix_lens)`` right after them: the device idles at that boundary for as long as the host needs
+        between the two (round 4, tools/stage_hole_probe.py: 270 -> 94 us at ViT-L B = 128, 181 -> 123 us at ViT-H B = 32)."""
+        return self._prepare(self._anchor_target(anchor, objective), tokens, rho, want_features, want_loss, seq_lens, kv, single_edit)
 
-    def score_candidates_run(self, plan, prefix_lens):
+    def _prepare(self, target, tokens, rho, want_features, want_loss, seq_lens, kv: _KvCache, single_edit) -> _ScorePlan:
+        full = np.ascontiguousarray(np.asarray(_host_lens(tokens) if seq_lens is None else seq_lens).reshape(-1), dtype=np.int32)
+        self._check_cache(kv, target.B, rho, full, single_edit)
+        host = torch.zeros(2 * full.size + 1, dtype=torch.int32, pin_memory=True)      # [cu (n + 1), cu[0] = 0 | prefix (n)]
+        t = self._candidates(tokens, target.B, rho)
+        args, ret = target.bind(rho, self.cfg.embed_dim, want_features, want_loss)
+        ws = self._workspace(1, full.size)
+        # the C entry; its arguments in front of and behind the three that ``score_candidates_run`` computes
+        fn, front = getattr(self._lib, target.prefix), (self._h, *self._weights(), _ptr(t))
+        back = (_ptr(kv.base_cu), _ptr(kv.buf), kv.base_rows, int(full.max()), *args, _ptr(ws), ws.numel())
+
+        def call(suf, cu, pfx):
+            _lib.check(fn(*front, suf, cu, pfx, *back, self._stream()), target.prefix)
+        return _ScorePlan(full, _prefix_limit(full, kv.lens, rho), host, t, rho, kv, bool(single_edit), target, ws, ret, call)
+
+    def score_candidates_run(self, plan: _ScorePlan, prefix_lens):
         """The prefix-dependent rest of ``score_candidates_prepare``: row plan (suffix rows per candidate, their running sum), one
         host-to-device copy, the launches.  Returns what ``score_candidates`` (``score_candidates_cls``) returns."""
-        full, n, kv = plan["full"], plan["full"].size, plan["kv"]
-        hv = plan["host"].numpy()
-        pfx = hv[n + 1:]
-        np.minimum(np.asarray(prefix_lens).reshape(-1), plan["limit"], out=pfx, casting="unsafe")
+        full, n, cache = plan.full, plan.full.size, plan.cache
+        hv = plan.host.numpy()
+        pfx = _clamp_prefix(prefix_lens, plan.limit, hv[n + 1:])
         suf = full - pfx                                                       # rows to compute per candidate (int32, contiguous)
-        hv[0] = 0
         np.cumsum(suf, out=hv[1:n + 1])
-        dev = plan["host"].to(self.device, non_blocking=True)
-        cu_dev, pfx_dev = dev[:n + 1], dev[n + 1:]
+        dev = plan.host.to(self.device, non_blocking=True)
         self.rows_scored += int(hv[n])
-        single_edit = plan["single_edit"]
-        if single_edit and os.environ.get("LEAF_VERIFY_SINGLE_EDIT") == "1":
-            if kv.get("tokens") is None:
-                raise ValueError("LEAF_VERIFY_SINGLE_EDIT: the K/V cache does not carry its captions' tokens")
-            verify_single_edit(plan["t"], full, pfx, kv["tokens"], kv["lens"], plan["rho"])
-        self._single_edit_call(single_edit, lambda: _lib.check(plan["fn"](
-            *plan["head"], C.c_void_p(suf.ctypes.data), _ptr(cu_dev), _ptr(pfx_dev), *plan["tail"], self._stream()), plan["entry"]))
-        return plan["ret"]
+        self._single_edit_call(plan.single_edit, lambda: plan.call(C.c_void_p(suf.ctypes.data), _ptr(dev[:n + 1]), _ptr(dev[n + 1:])),
+                               (plan.tokens, full, pfx, cache.tokens, cache.lens, plan.rho))
+        return plan.ret
 
     # ------------------------------------------------------------------ classification scoring (classify.hip)
     def _cls_target(self, class_features, labels, want_pred, want_logits):
@@ -643,11 +698,8 @@ class LeafCLIPText:
         classes.  loss[b, r] = max_{c != labels[b]} logit[c] - logit[labels[b]], pred[b, r] = first arg-max of the logits.
         Returns (best_idx int32 [B], best_feat [B, D] or None, loss [B, rho] or None, pred int32 [B, rho] or None,
         logits [B * rho, C] or None).  ``prefix_lens`` / ``kv``: prefix reuse as in ``score_candidates``; same bits."""
-        cls = self._cls_target(class_features, labels, want_pred, want_logits)
-        if prefix_lens is not None and kv is not None and self.trim_rows:
-            return self.score_candidates_run(
-                self.score_candidates_prepare(tokens, None, rho, "l2", want_features, want_loss, seq_lens=seq_lens, kv=kv, cls=cls), prefix_lens)
-        return self._score_dense(cls, tokens, rho, want_features, want_loss, seq_lens)
+        return self._score(self._cls_target(class_features, labels, want_pred, want_logits), tokens, rho, want_features, want_loss,
+                           seq_lens, prefix_lens, kv)
 
     def score_candidates_fused(self, base_tokens, base_lens, tokens, anchor: torch.Tensor, rho: int, seq_lens, prefix_lens,
                                objective: str = "l2", want_features: bool = False, want_loss: bool = False, single_edit: bool = False):
@@ -655,49 +707,34 @@ class LeafCLIPText:
         (leaf_score_candidates_prefix_fused: the B clean captions ride in the launches of their B*rho candidates).
         Returns (best_idx, best_feat or None, kv cache for the later stages[, loss [B, rho] when want_loss]), or None when
         the rows do not fit one chunk (the caller then uses the two separate calls).  Bit-identical to the separate calls.
+        The pass fills cache slot 0, the one ``encode_text_kv`` fills by default: earlier caches of that slot are stale once it succeeds.
         ``single_edit``: as in ``score_candidates``; the cache it returns then holds the captions' layer-0 Q rows, which the later
         single_edit stages read (a cache of a pass without it does not, and such a stage refuses it)."""
-        if not self._packed:
-            self.pack()
-        B = anchor.shape[0]
+        target = self._anchor_target(anchor, objective)
+        B = target.B
         blens = np.ascontiguousarray(np.asarray(base_lens).reshape(-1), dtype=np.int32)
-        full = np.asarray(seq_lens, dtype=np.int64).reshape(-1)
-        pfx = np.minimum(np.asarray(prefix_lens, dtype=np.int64).reshape(-1), full - 1)      # keep at least the EOT row
-        pfx = np.minimum(pfx, np.repeat(blens.astype(np.int64), rho))                        # rows the captions really have
-        lens, cu = _lens_cu(np.concatenate([blens, full - pfx]))                             # rows to compute per sequence
-        host = np.concatenate([cu, np.zeros(B, dtype=np.int32), pfx.astype(np.int32)])
-        dev = torch.from_numpy(host).pin_memory().to(self.device, non_blocking=True)
-        cu_dev, pfx_dev = dev[:lens.size + 1], dev[lens.size + 1:]
-        bt = self._tokens(base_tokens)
-        ct = self._tokens(tokens.reshape(-1, tokens.shape[-1]))
-        if bt.shape[0] != B or ct.shape[0] != B * rho:
-            raise ValueError("captions / candidate rows do not match B, B*rho")
+        full = np.asarray(seq_lens).reshape(-1).astype(np.int32)
         if single_edit:
-            if not np.array_equal(full, np.repeat(blens.astype(np.int64), rho)):
-                raise ValueError("single_edit pass: a candidate's length differs from its caption's")
-            if os.environ.get("LEAF_VERIFY_SINGLE_EDIT") == "1":
-                verify_single_edit(ct, full, pfx, bt, blens, rho)
-        t = torch.cat([bt, ct], 0)
-        base_rows = int(cu[B])
-        kvbuf = self._kv_buffer(0, base_rows)              # slot 0: the one encode_text_kv fills by default
-        anchor = anchor.to(device=self.device, dtype=torch.float32).contiguous()
-        idx = torch.empty(B, dtype=torch.int32, device=self.device)
-        feat = torch.empty(B, self.cfg.embed_dim, dtype=torch.float32, device=self.device) if want_features else None
-        loss = torch.empty(B, rho, dtype=torch.float32, device=self.device) if want_loss else None
+            _check_equal_lengths(full, blens, rho)
+        pfx = _clamp_prefix(prefix_lens, _prefix_limit(full, blens, rho), np.empty(full.size, dtype=np.int32))
+        lens, cu = _lens_cu(np.concatenate([blens, full - pfx]))                             # rows to compute per sequence
+        # [cu (B + n + 1) | prefix (B + n): the captions' own is 0]
+        dev = torch.from_numpy(np.concatenate([cu, np.zeros(B, dtype=np.int32), pfx])).pin_memory().to(self.device, non_blocking=True)
+        bt, ct = self._candidates(base_tokens, B), self._candidates(tokens, B, rho)
+        t, weights = torch.cat([bt, ct], 0), self._weights()
+        kvbuf = self._kv_buffer(0, int(cu[B]))
+        args, ret = target.bind(rho, self.cfg.embed_dim, want_features, want_loss)
         ws = self._workspace(1, B + B * rho)
-        max_len = int(max(int(full.max()), int(blens.max())))
         rc = self._single_edit_call(single_edit, lambda: self._lib.leaf_score_candidates_prefix_fused(
-            self._h, _ptr(self.flat), _ptr(self.w16), _ptr(t), C.c_void_p(lens.ctypes.data), _ptr(cu_dev), _ptr(pfx_dev), max_len,
-            _ptr(anchor), B, rho, _OBJ[objective], _ptr(idx), _ptr(feat), _ptr(loss), _ptr(kvbuf), kvbuf.numel(),
-            _ptr(ws), ws.numel(), self._stream()))
+            self._h, *weights, _ptr(t), C.c_void_p(lens.ctypes.data), _ptr(dev[:lens.size + 1]), _ptr(dev[lens.size + 1:]),
+            max(int(full.max()), int(blens.max())), *args, _ptr(kvbuf), kvbuf.numel(), _ptr(ws), ws.numel(), self._stream()),
+            (ct, full, pfx, bt, blens, rho))
         if rc == 2:
             return None
         _lib.check(rc, "leaf_score_candidates_prefix_fused")
         self.rows_scored += int(cu[-1])
         # q0: without single_edit the fused launch keeps the captions' Q rows on chip, layer 0 of the cache holds K and V only
-        cache = {"kv": kvbuf, "base_cu": cu_dev[:B + 1], "base_rows": base_rows, "lens": blens, "n": B, "arith": self.arithmetic_tag(),
-                 "q0": bool(single_edit), "tokens": bt}
-        return (idx, feat, cache, loss) if want_loss else (idx, feat, cache)
+        return (*ret[:2], self._kv_cache(kvbuf, dev[:B + 1], int(cu[B]), blens, bool(single_edit), bt, 0), *ret[2:])
 
     # ------------------------------------------------------------------ training
     def enable_training(self):
@@ -736,8 +773,6 @@ class LeafCLIPText:
         if delta is not None and (delta.dtype != torch.float32 or not delta.is_contiguous() or delta.numel() != rows * self.cfg.width):
             raise ValueError(f"delta must be contiguous fp32 with {rows} x {self.cfg.width} elements")
         self.enable_training()
-        if not self._packed:
-            self.pack()
         plan.place(self.device)
         t = self._tokens(text)
         n = t.shape[0]
@@ -748,7 +783,7 @@ class LeafCLIPText:
         if self._lib.leaf_text_get_option(self._h, b"normalize_fare") != int(bool(normalize)):
             self.set_option("normalize_fare", int(bool(normalize)))
         entry, extra = ("leaf_text_forward_train_last", ()) if pool_last else ("leaf_text_forward_train_delta", (_ptr(delta),))
-        _lib.check(getattr(self._lib, entry)(self._h, _ptr(self.flat), _ptr(self.w16), _ptr(t), plan.lens_ptr, plan.cu_ptr, n, *extra,
+        _lib.check(getattr(self._lib, entry)(self._h, *self._weights(), _ptr(t), plan.lens_ptr, plan.cu_ptr, n, *extra,
                                              _ptr(out), _ptr(stash), stash.numel(), _ptr(ws), ws.numel(), self._stream()), entry)
         self.stash_ticket += 1
         self.train_pass = _TrainPass(t, plan, n, rows, bool(normalize), bool(pool_last), self.stash_ticket)

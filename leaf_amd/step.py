@@ -137,7 +137,7 @@ def search_synthetic(model, anchor: torch.Tensor, base: torch.Tensor, cfg: StepC
         # arrival on the host and that call's first launch)
         # (the second stage looks block 0's rows up only in a cache that holds the captions' layer-0 Q rows: one written by a first
         # stage that ran with the option, or by encode_text_kv)
-        single2 = single and kv is not None and bool(kv.get("q0"))
+        single2 = single and kv is not None and kv.q0
         plan2 = model.score_candidates_prepare(cand.view(B * cfg.rho, -1), anchor, cfg.rho, "l2", want_features=False,
                                                seq_lens=cand_lens, kv=kv, single_edit=single2) if reuse and kv is not None else None
         pos2 = gen.stage2_positions(pos, best1.cpu().numpy())           # the search's device->host sync (B indices)

@@ -451,7 +451,7 @@ def test_default_arithmetic_is_the_priced_split_policy_and_keeps_every_exactness
     z = np.load(os.path.join(golden_dir, "vitl_quickgelu.npz"))
     m = create_model("ViT-L-14-quickgelu", seed=1)
     from leaf_amd.model import PRECISION_MODES
-    assert m.split_masks == PRECISION_MODES["rowsafe"] and m.precision_name() == "rowsafe" and m.arithmetic_tag() == (1, PRECISION_MODES["rowsafe"])
+    assert m.split_masks == PRECISION_MODES["rowsafe"] and m.precision_name() == "rowsafe" and m.arithmetic_tag() == (1, PRECISION_MODES["rowsafe"], 1)
     toks = z["tokens"]
     r_def = row_rel_l2(m.encode_text(toks).cpu().numpy(), z["out"])
     fast = create_model("ViT-L-14-quickgelu", seed=1).set_precision("fast")
@@ -459,7 +459,7 @@ def test_default_arithmetic_is_the_priced_split_policy_and_keeps_every_exactness
     print(f"[default arithmetic] rows max / median: rowsafe {r_def.max():.3e} / {np.median(r_def):.3e}   fast {r_fast.max():.3e} / {np.median(r_fast):.3e}")
     assert r_def.max() < 8.8e-4 and np.median(r_def) < 0.88 * np.median(r_fast)
     frozen = LeafCLIPText(get_config("ViT-L-14-quickgelu")).copy_from(fast)
-    assert frozen.arithmetic_tag() == fast.arithmetic_tag() == (1, ())
+    assert frozen.arithmetic_tag() == fast.arithmetic_tag() == (1, (), 1)
     assert np.array_equal(frozen.encode_text(toks).cpu().numpy(), fast.encode_text(toks).cpu().numpy())
     B, rho = 6, 50
     base = O.synthetic_tokens(B, seed=61, min_len=20, max_len=50)

@@ -167,13 +167,11 @@ def test_vitl_k5_search_every_stage_rescored_by_oracle(torch_mod):
     real_prep, real_run = m.score_candidates_prepare, m.score_candidates_run
 
     def spy_prep(tokens, anchor_, rho_, objective="l2", want_features=True, want_loss=False, **kw):
-        plan = real_prep(tokens, anchor_, rho_, objective, want_features=True, want_loss=True, **kw)
-        plan["_tokens"] = tokens
-        return plan
+        return real_prep(tokens, anchor_, rho_, objective, want_features=True, want_loss=True, **kw)
 
     def spy_run(plan, prefix_lens):
         idx, feat, loss = real_run(plan, prefix_lens)
-        calls.append((plan["_tokens"].detach().cpu().numpy().copy(), idx.cpu().numpy().copy(), loss.cpu().numpy().copy(),
+        calls.append((plan.tokens.detach().cpu().numpy().copy(), idx.cpu().numpy().copy(), loss.cpu().numpy().copy(),
                       feat.cpu().numpy().copy()))
         return idx, feat
     m.score_candidates = spy

@@ -77,8 +77,8 @@ def test_fused_qkv_attention_is_bit_identical_packed_and_prefix(torch_mod, model
         i2, f2, l2 = m.score_candidates(flat, anchor, rho, "l2", want_loss=True, seq_lens=lens, prefix_lens=pl, kv=cache)
         # the cache's K and V thirds (layout [layers][rows][q | k | v]): with the fused launch the captions' q rows are not written
         # there at all -- nothing reads them (a caption's own attention runs inside the launch)
-        rows, dd = cache["base_rows"], m.cfg.width
-        kvv = cache["kv"][: rows * 3 * dd * 2 * m.cfg.layers].view(torch_mod.int16).view(m.cfg.layers, rows, 3 * dd)[:, :, dd:]
+        rows, dd = cache.base_rows, m.cfg.width
+        kvv = cache.buf[: rows * 3 * dd * 2 * m.cfg.layers].view(torch_mod.int16).view(m.cfg.layers, rows, 3 * dd)[:, :, dd:]
         return (i, f, l), (i2, f2, l2), kvv.clone()
     (e1, e2, kvbytes1), (g1, g2, kvbytes0) = _both(m, fused_stage)
     _eq(torch_mod, e1, g1, "fused caption pass")

@@ -146,7 +146,7 @@ def test_single_edit_replaces_the_fused_launch_of_block_0(torch_mod, precision):
     def stage1(se):
         return lambda: m.score_candidates_fused(base, bl, flat, anchor, rho, lens, pos.reshape(-1), single_edit=se)
 
-    for stage in (stage1, stage2):
+    for stage in (stage2, stage1):      # stage 2 first: the fused first stage rewrites the slot that ``kv`` names
         off = launch_families(stage(False))
         on = launch_families(stage(True))
         fused = lambda f: sum(c for (fam, e, N, K), c in f.items() if fam == 8 and N == 3 * d)

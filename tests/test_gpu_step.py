@@ -83,21 +83,21 @@ def test_fused_caption_pass_is_bit_identical(name, B, rho):
     cand, pos = gen.stage1(base)
     cand_lens = np.repeat(lens, rho)
     kv_a = m.encode_text_kv(base, seq_lens=lens)
-    need = kv_a["base_rows"] * 3 * m.cfg.width * 2 * m.cfg.layers
-    kv_bytes_a = kv_a["kv"][:need].clone()
+    need = kv_a.base_rows * 3 * m.cfg.width * 2 * m.cfg.layers
+    kv_bytes_a = kv_a.buf[:need].clone()
     i_a, f_a = m.score_candidates(cand.view(B * rho, -1), anchor, rho, "l2", seq_lens=cand_lens, prefix_lens=pos.reshape(-1), kv=kv_a)
     i_a, f_a = i_a.clone(), f_a.clone()
-    kv_a["kv"].zero_()
+    kv_a.buf.zero_()
     fused = m.score_candidates_fused(base, lens, cand.view(B * rho, -1), anchor, rho, cand_lens, pos.reshape(-1), want_features=True)
     assert fused is not None
     i_b, f_b, kv_b = fused
     assert torch.equal(i_a, i_b) and torch.equal(f_a, f_b)
     # ... the K and V thirds of every cached row ([layers][rows][q | k | v]; the fused pass does not write the captions' q rows into the
     # cache: no consumer reads them)
-    rows_, dd = kv_a["base_rows"], m.cfg.width
+    rows_, dd = kv_a.base_rows, m.cfg.width
     kvv = lambda t: t.view(torch.int16).view(m.cfg.layers, rows_, 3 * dd)[:, :, dd:]
-    assert torch.equal(kvv(kv_bytes_a), kvv(kv_b["kv"][:need]))
-    assert kv_b["base_rows"] == kv_a["base_rows"] and torch.equal(kv_a["base_cu"].cpu(), kv_b["base_cu"].cpu())
+    assert torch.equal(kvv(kv_bytes_a), kvv(kv_b.buf[:need]))
+    assert kv_b.base_rows == kv_a.base_rows and torch.equal(kv_a.base_cu.cpu(), kv_b.base_cu.cpu())
     # a later stage from the fused pass's cache
     cand2 = gen.stage2_device(base, i_b)
     pos2 = gen.stage2_positions(pos, i_b.cpu().numpy())
