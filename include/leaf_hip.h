@@ -44,8 +44,7 @@ int leaf_version(void);
 /* handle: replaces open_clip.factory.create_model's text tower construction (model.py:173-217) */
 int leaf_text_create(const leaf_text_cfg* cfg, int fwd_dtype, leaf_text_t* out);
 void leaf_text_destroy(leaf_text_t h);
-int leaf_text_set_chunk(leaf_text_t h, int seqs_per_chunk); /* sequences processed per pass through the layers */
-/* options: "chunk" (as above), "last_layer_trim" (0/1, default 1: the last block's attention output, out-projection and
+/* options: "chunk" (sequences processed per pass through the layers, >= 1), "last_layer_trim" (0/1, default 1: the last block's attention output, out-projection and
  * MLP are computed for the pooled EOT row only -- exact, every op after attention is row-wise), "compact_resid" (0/1, default 1:
  * the residual stream of the LN-folded forward-only passes as the 16-bit copy + a remainder byte per element instead of an fp32
  * row beside that copy -- see leaf_op_gemm_resid_ln8 below; 0, or LEAF_COMPACT_RESID=0, keeps fp32 rows), "single_edit" (0/1, default 0: see "single-edit passes" below), and the A/B switches "ln_fold", "fuse_attn", "normalize_fare" */
@@ -70,15 +69,13 @@ int leaf_text_pack_weights(leaf_text_t h, const float* params, void* w16_fwd, vo
  * forward_kv; the training forward is untouched -- the reference trains under fp16 autocast, utils_AT.py:317-319).  A split GEMM
  * multiplies hi + lo 16-bit splits (x_hi W_hi + x_lo W_hi + x_hi W_lo in the fp32 accumulator, over a longer K through the unchanged
  * GEMM kernels -- the fused QKV + attention launch included; stored q|k|v / attention / hidden rows stay 16-bit).  The embedding's
- * error is made early (profiles/r06_precision_budget_sites.txt).  leaf_text_split_pack: all four GEMMs of the
- * first `blocks` blocks (QKV / c_fc both operands, out_proj / c_proj weights).  leaf_text_split_pack_masks: one mask per block,
- * bit 0 = QKV, bit 1 = out_proj, bit 2 = c_fc, bit 3 = c_proj -- leaf_amd's default arithmetic is such a mask list
- * (leaf_amd/model.py PRECISION_MODES; profiles/r06_row_error_census*.txt).  Works on both residual-stream formats
- * ("compact_resid").  `buf` (DEVICE, leaf_text_split_bytes(h, blocks) bytes, caller-owned, must outlive the calls that use it)
+ * error is made early (profiles/r06_precision_budget_sites.txt).  leaf_text_split_pack_masks: one mask per block,
+ * bit 0 = QKV (both operands), bit 1 = out_proj (weights), bit 2 = c_fc (both operands), bit 3 = c_proj (weights) -- leaf_amd's default
+ * arithmetic is such a mask list (leaf_amd/model.py PRECISION_MODES; profiles/r06_row_error_census*.txt).  Works on both
+ * residual-stream formats ("compact_resid").  `buf` (DEVICE, leaf_text_split_bytes(h, blocks) bytes, caller-owned, must outlive the calls that use it)
  * receives the split weight copies; call again after every optimizer step (as leaf_text_pack_weights).  blocks = 0 (buf ignored)
  * switches splits off.  0 <= blocks <= min(layers - 1, 64); needs option ln_fold = 1. */
 size_t leaf_text_split_bytes(leaf_text_t h, int blocks);
-int leaf_text_split_pack(leaf_text_t h, const float* params, int blocks, void* buf, leaf_stream_t s);
 int leaf_text_split_pack_masks(leaf_text_t h, const float* params, const int32_t* masks, int blocks, void* buf, leaf_stream_t s);
 
 /* workspace sizes (bytes): mode 0 = forward, 1 = score_candidates, 2 = train backward */
@@ -106,13 +103,39 @@ int leaf_text_forward_precise(leaf_text_t h, const float* params, const int32_t*
                               const int32_t* cu_rows, int n_seq, float* out, int normalize, void* ws, size_t ws_bytes,
                               leaf_stream_t s);
 
-/* one search stage of attack_text_leaf (utils_attacks.py:330-348 / 368-386,393): forward of B*rho candidates,
- * loss per objective against anchor [B,embed_dim], first-index arg-max over rho, gather of the winning rows.
- * loss (fp32 [B,rho]) and best_feat (fp32 [B,embed_dim]) may be NULL. */
-int leaf_score_candidates(leaf_text_t h, const float* params, const void* w16_fwd, const int32_t* tokens,
-                          const int32_t* seq_lens, const int32_t* cu_rows, const float* anchor, int B, int rho,
-                          int objective, int32_t* best_idx, float* best_feat, float* loss, void* ws, size_t ws_bytes,
-                          leaf_stream_t s);
+/* One search stage of attack_text_leaf (utils_attacks.py:330-348 / 368-386,393): forward of the B*rho candidates in `tokens`, a loss
+ * per candidate, the best of the rho candidates of each caption into best_idx [B] (int32) and its feature row into best_feat (fp32
+ * [B,embed_dim], may be NULL); loss: fp32 [B,rho].  Every argument is a named field; `size` = sizeof(leaf_score_args), checked.
+ * Exactly ONE target: `anchor` [B,embed_dim] with `objective` (LEAF_OBJ_*; first-index arg-max over rho, loss may be NULL), or
+ * `class_feat` -- the classification score (leaf_amd/csrc/classify.hip; attack_text_charmer_classification, utils_attacks.py:582-643):
+ * L2-normalised features against a class matrix shared by all captions.  class_feat [C, embed_dim] (fp32, device, unit rows: the
+ * caller normalises), labels [B] (int32, device, each in [0, C): the caller checks, the engine cannot), LEAF_CLS_MIN_CLASSES <= C <=
+ * LEAF_CLS_MAX_CLASSES (an error outside).
+ *   logit[c] = <feat[b,r], class_feat[c]>;  loss[b,r] = max_{c != labels[b]} logit[c] - logit[labels[b]] (margin_loss_lm, :145-151;
+ *   NaN when a logit is NaN);  pred[b,r] = first arg-max of logit over c (:630-631).
+ * loss is REQUIRED with it (best_idx is taken from it); pred (int32 [B,rho]) and logits (fp32 [B*rho, C]) may be NULL.  best_idx[b] =
+ * the first of loss[b,:] in the order of leaf_select_topk (NaN first, larger value, lower column).  A candidate's logits, loss and pred
+ * do not depend on B, rho, its place in the launch or the grouping of captions into launches: each inner product is summed in one
+ * fixed order.
+ * The rows of the pass, by the fields (results are bit-identical in all three):
+ *   prefix == NULL: all kept rows (seq_lens / cu_rows as in leaf_text_forward, both NULL = dense); kv, base_cu, kv_write NULL / 0.
+ *   prefix != NULL, kv_write == 0: "prefix reuse" over the cache `kv` of leaf_text_forward_kv below; seq_lens / cu_rows (then the rows
+ *     to COMPUTE per candidate and their prefix sum), base_cu, kv and base_rows are required.
+ *   kv_write != 0: the fused first stage below: `kv` (kv_bytes) is written.  Anchor target only. */
+#define LEAF_CLS_MIN_CLASSES 2
+#define LEAF_CLS_MAX_CLASSES 1024
+typedef struct leaf_score_args {
+    uint32_t size;
+    const float* params; const void* w16_fwd;                                                    /* weights */
+    const int32_t *tokens, *seq_lens /* HOST */, *cu_rows;                                       /* rows */
+    const int32_t *prefix, *base_cu; void* kv; size_t base_rows, kv_bytes; int32_t max_len, kv_write; /* prefix reuse */
+    int32_t B, rho;
+    const float* anchor; int32_t objective;                                                      /* anchor target */
+    const float* class_feat; int32_t C; const int32_t* labels; int32_t* pred; float* logits;     /* class target */
+    int32_t* best_idx; float *best_feat, *loss;                                                  /* outputs */
+    void* ws; size_t ws_bytes; leaf_stream_t stream;
+} leaf_score_args;
+int leaf_score_pass(leaf_text_t h, const leaf_score_args* a);
 
 /* Segmented top-n selection (leaf_amd/csrc/select.hip; Charmer's position pick and arg-max, leaf_amd/charmer.py): per row b of
  * loss [B, ld] (fp32, device) the min(n, count[b]) largest of columns [0, count[b]) in descending order -- ties -> lower column
@@ -126,106 +149,58 @@ int leaf_select_topk(const float* loss, int ld, const int32_t* count, int B, int
 /* Exact work skipping, part 2 ("prefix reuse"): a search candidate equals its clean caption at every
  * position before its first changed token, and under the causal mask those rows are identical at every layer.
  * leaf_text_forward_kv runs the clean captions once and keeps each layer's q|k|v rows in `kv` (leaf_text_kv_bytes);
- * leaf_score_candidates_prefix then computes, for candidate i of caption i / rho, only positions
- * [prefix[i], prefix[i] + suffix_lens[i]) and reads the K/V of earlier positions from the cache.  cu_suffix = exclusive
- * prefix sum of suffix_lens (device), base_cu = packed row offsets of the captions inside the cache (device, [B+1]),
- * base_rows = total cached rows per layer, max_len = an upper bound of prefix[i] + suffix_lens[i] over the candidates
- * (sizes the attention kernel's LDS; 0 = context_length).  Results are bit-identical to leaf_score_candidates. */
+ * leaf_score_pass with `prefix` (device, [B*rho]) then computes, for candidate i of caption i / rho, only positions
+ * [prefix[i], prefix[i] + seq_lens[i]) and reads the K/V of earlier positions from the cache.  seq_lens = the suffix lengths (host),
+ * cu_rows = their exclusive prefix sum (device), base_cu = packed row offsets of the captions inside the cache (device, [B+1]),
+ * base_rows = total cached rows per layer, max_len = an upper bound of prefix[i] + seq_lens[i] over the candidates
+ * (sizes the attention kernel's LDS; 0 = context_length).  Results are bit-identical to the pass without `prefix`. */
 size_t leaf_text_kv_bytes(leaf_text_t h, int n_seq);
 int leaf_text_forward_kv(leaf_text_t h, const float* params, const void* w16_fwd, const int32_t* tokens,
                          const int32_t* seq_lens, const int32_t* cu_rows, int n_seq, float* out /* may be NULL */,
                          int normalize, void* kv, size_t kv_bytes, void* ws, size_t ws_bytes, leaf_stream_t s);
-int leaf_score_candidates_prefix(leaf_text_t h, const float* params, const void* w16_fwd, const int32_t* tokens,
-                                 const int32_t* suffix_lens, const int32_t* cu_suffix, const int32_t* prefix,
-                                 const int32_t* base_cu, const void* kv, size_t base_rows, int max_len,
-                                 const float* anchor, int B, int rho, int objective, int32_t* best_idx, float* best_feat, float* loss, void* ws,
-                                 size_t ws_bytes, leaf_stream_t s);
-
-/* leaf_text_forward_kv and the FIRST stage's leaf_score_candidates_prefix in one pass (the clean-caption pass is a chain of ~80
- * small launches; here its 3,200 rows ride in the candidates' launches): tokens [(B + B*rho), ctx] with the B captions FIRST,
+/* leaf_text_forward_kv and the FIRST stage's prefix pass in one (leaf_score_pass with kv_write != 0; the clean-caption pass is a chain
+ * of ~80 small launches; here its 3,200 rows ride in the candidates' launches): tokens [(B + B*rho), ctx] with the B captions FIRST,
  * seq_lens (host) = rows to compute per sequence (captions: their length; candidates: suffix length), cu_rows = exclusive
- * prefix sum (device, [B + B*rho + 1]), prefix (device; 0 for the captions).  `kv` receives the captions' per-layer q|k|v rows
- * exactly as leaf_text_forward_kv writes them (later stages use leaf_score_candidates_prefix with it).  Bit-identical
- * results.  Returns 2 when the rows do not fit one chunk (use the two separate calls then). */
-int leaf_score_candidates_prefix_fused(leaf_text_t h, const float* params, const void* w16_fwd, const int32_t* tokens,
-                                       const int32_t* seq_lens, const int32_t* cu_rows, const int32_t* prefix, int max_len,
-                                       const float* anchor, int B, int rho, int objective, int32_t* best_idx, float* best_feat,
-                                       float* loss, void* kv, size_t kv_bytes, void* ws, size_t ws_bytes, leaf_stream_t s);
-
-/* Zero-shot classification scoring (leaf_amd/csrc/classify.hip; attack_text_charmer_classification, utils_attacks.py:582-643): the
- * pass of leaf_score_candidates with L2-normalised features, scored against a class matrix shared by all captions instead of one
- * anchor row per caption.  class_feat [C, embed_dim] (fp32, device, unit rows: the caller normalises), labels [B] (int32, device,
- * each in [0, C): the caller checks, the engine cannot), LEAF_CLS_MIN_CLASSES <= C <= LEAF_CLS_MAX_CLASSES (an error outside).
- *   logit[c] = <feat[b,r], class_feat[c]>;  loss[b,r] = max_{c != labels[b]} logit[c] - logit[labels[b]] (margin_loss_lm, :145-151;
- *   NaN when a logit is NaN);  pred[b,r] = first arg-max of logit over c (:630-631).
- * loss [B,rho] is REQUIRED here (best_idx is taken from it); pred (int32 [B,rho]), logits (fp32 [B*rho, C]) and best_feat may be
- * NULL.  best_idx[b] = the first of loss[b,:] in the order of leaf_select_topk (NaN first, larger value, lower column).  A
- * candidate's logits, loss and pred do not depend on B, rho, its place in the launch or the grouping of captions into launches:
- * each inner product is summed in one fixed order.  leaf_score_candidates_prefix_cls: the same under prefix reuse (arguments
- * as leaf_score_candidates_prefix); bit-identical results. */
-#define LEAF_CLS_MIN_CLASSES 2
-#define LEAF_CLS_MAX_CLASSES 1024
-int leaf_score_candidates_cls(leaf_text_t h, const float* params, const void* w16_fwd, const int32_t* tokens,
-                              const int32_t* seq_lens, const int32_t* cu_rows, const float* class_feat, int C,
-                              const int32_t* labels, int B, int rho, int32_t* best_idx, float* best_feat, float* loss,
-                              int32_t* pred, float* logits, void* ws, size_t ws_bytes, leaf_stream_t s);
-int leaf_score_candidates_prefix_cls(leaf_text_t h, const float* params, const void* w16_fwd, const int32_t* tokens,
-                                     const int32_t* suffix_lens, const int32_t* cu_suffix, const int32_t* prefix,
-                                     const int32_t* base_cu, const void* kv, size_t base_rows, int max_len,
-                                     const float* class_feat, int C, const int32_t* labels, int B, int rho, int32_t* best_idx,
-                                     float* best_feat, float* loss, int32_t* pred, float* logits, void* ws, size_t ws_bytes,
-                                     leaf_stream_t s);
+ * prefix sum (device, [B + B*rho + 1]), prefix (device; 0 for the captions); base_cu NULL (the captions' offsets are cu_rows' first).
+ * `kv` receives the captions' per-layer q|k|v rows exactly as leaf_text_forward_kv writes them (later stages are prefix passes over
+ * it).  Bit-identical results.  Returns 2 when the rows do not fit one chunk (use the two separate calls then). */
 
 /* Exact work skipping, part 3 ("single-edit passes"; option "single_edit" of leaf_text_set_option, 0/1, default 0, set by the caller
  * for the passes it holds for).  Block 0's q|k|v row is LN1(E[token] + P[position]) W_qkv + b: it depends on the pair (token,
- * position) and on nothing else.  With the option set the caller PROMISES, for every candidate i of a leaf_score_candidates_prefix /
- * _prefix_fused pass, that it is its caption with ONE token replaced at position prefix[i]: equal lengths, and every token BEHIND
+ * position) and on nothing else.  With the option set the caller PROMISES, for every candidate i of a prefix or fused
+ * leaf_score_pass, that it is its caption with ONE token replaced at position prefix[i]: equal lengths, and every token BEHIND
  * prefix[i] equal to the caption's at the same position (in front of it: the promise prefix reuse makes already).  Of the rows a
  * candidate computes only row prefix[i] then has a pair its caption does not have; block 0 projects that one row per candidate (one
  * small GEMM) and its attention reads every other q|k|v row -- Q included -- from layer 0 of the captions' cache.  Every later
  * block is unchanged and the results are bit-identical.  The cache must hold the captions' Q rows of layer 0: leaf_text_forward_kv
- * writes them; leaf_score_candidates_prefix_fused writes them only when it runs with the option set itself (without it the captions' Q rows never
+ * writes them; the fused pass writes them only when it runs with the option set itself (without it the captions' Q rows never
  * leave the chip), so a cache from a fused pass WITHOUT the option must not be handed to a pass WITH it (leaf_amd/model.py keeps
  * that flag beside the cache and refuses).  The engine cannot check the promise (the tokens are on the device); a broken one gives
  * wrong scores.  Passes the mode does not take (ln_fold = 0, dense rows, no prefix map, a one-block tower) run as without the
  * option.  For token-level substitutions (leaf_amd/step.py, the benchmark's synthetic search); NOT for the character-level string
  * search (leaf_amd/attacks.py, charmer.py): a character edit re-tokenises the rest of the caption. */
 
-/* training forward (utils_AT.py:317-319) keeping activations in `stash` for the backward pass */
-int leaf_text_forward_train(leaf_text_t h, const float* params, const void* w16_fwd, const int32_t* tokens,
-                            const int32_t* seq_lens, const int32_t* cu_rows, int n_seq, float* out, void* stash,
-                            size_t stash_bytes, void* ws, size_t ws_bytes, leaf_stream_t s);
+/* Training forward (utils_AT.py:317-319) keeping activations in `stash` (leaf_text_stash_bytes) for the backward pass: tokens
+ * [n_seq, ctx] -> out fp32 [n_seq, embed_dim]; `size` = sizeof(leaf_train_fwd_args), checked.
+ * delta (may be NULL): the OPTIONAL embedding-space PGD mode (no reference path runs it on text, the pieces are
+ * the reference's): forward of tokens whose embeddings carry an additive perturbation delta (fp32 [rows, width], packed like the
+ * activations, resident in HBM across the inner iterations) - the embedding-input forward of src/pez/open_clip_pez/model.py:210-228
+ * fused into the embedding gather + first LayerNorm.
+ * pool_last != 0: text embedding inversion (PEZ: src/pez/optim_utils.py:26-55,139-232; leaf_amd/inversion.py).  The training forward
+ * for an INVERTED PROMPT [SOT, ids, EOT]: a projected id may itself be 49407 or 49406, so the pooled row is not "the first maximum
+ * token id" but the template's EOT slot (open_clip_pez/model.py:226 with the dummy ids of optim_utils.py:119-128), the LAST row of
+ * the sequence: the pass pools at row seq_lens[i] - 1 and keeps all seq_lens[i] rows whatever the ids are; seq_lens / cu_rows are
+ * REQUIRED, ws must hold n_seq x width floats, and delta must be NULL. */
+typedef struct leaf_train_fwd_args {
+    uint32_t size;
+    const float* params; const void* w16_fwd;
+    const int32_t *tokens, *seq_lens /* HOST */, *cu_rows; int32_t n_seq;
+    const float* delta; int32_t pool_last;
+    float* out; void* stash; size_t stash_bytes;
+    void* ws; size_t ws_bytes; leaf_stream_t stream;
+} leaf_train_fwd_args;
+int leaf_text_forward_train(leaf_text_t h, const leaf_train_fwd_args* a);
 
-/* OPTIONAL embedding-space PGD mode (no reference path runs it on text, the pieces are the
- * reference's): forward of tokens whose embeddings carry an additive perturbation delta (fp32 [rows, width], packed like
- * the activations, resident in HBM across the inner iterations; NULL = none) - the embedding-input forward of
- * src/pez/open_clip_pez/model.py:210-228 fused into the embedding gather + first LayerNorm. */
-int leaf_text_forward_train_delta(leaf_text_t h, const float* params, const void* w16_fwd, const int32_t* tokens,
-                                  const int32_t* seq_lens, const int32_t* cu_rows, int n_seq, const float* delta,
-                                  float* out, void* stash, size_t stash_bytes, void* ws, size_t ws_bytes, leaf_stream_t s);
-/* TextFARE loss of (anchor, feat) and ONLY its gradient with respect to the token embeddings / delta (fp32
- * [rows, width], un-scaled): the backward of the continuous attack loop (utils_attacks.py:683-692) without any
- * parameter gradient.  loss_out: one device float (mean over captions of the squared distance). */
-int leaf_textfare_input_grad(leaf_text_t h, const float* params, const void* w16_bwd, const int32_t* tokens,
-                             const int32_t* seq_lens, const int32_t* cu_rows, int n_seq, const float* feat,
-                             const float* anchor, const void* stash, float* d_embed, float* loss_out, void* ws,
-                             size_t ws_bytes, leaf_stream_t s);
-/* ---- text embedding inversion (PEZ: src/pez/optim_utils.py:26-55,139-232; leaf_amd/inversion.py) ----
- * The training forward for an INVERTED PROMPT [SOT, ids, EOT]: a projected id may itself be 49407 or 49406, so the pooled row is not
- * "the first maximum token id" but the template's EOT slot (open_clip_pez/model.py:226 with the dummy ids of optim_utils.py:119-128),
- * the LAST row of the sequence.  Same as leaf_text_forward_train except that it pools at row seq_lens[i] - 1 and keeps all
- * seq_lens[i] rows whatever the ids are; seq_lens / cu_rows are REQUIRED, ws must hold n_seq x width floats. */
-int leaf_text_forward_train_last(leaf_text_t h, const float* params, const void* w16_fwd, const int32_t* tokens,
-                                 const int32_t* seq_lens, const int32_t* cu_rows, int n_seq, float* out, void* stash,
-                                 size_t stash_bytes, void* ws, size_t ws_bytes, leaf_stream_t s);
-/* Cosine head + input-gradient-only backward (optim_utils.py:191-196 with prompt_bs = batch_size = 1, for n_seq independent
- * inversions at once): loss_b = loss_weight (1 - cos(feat_b, target_b)), the target normalised inside the head, fp32; d_embed (fp32
- * [rows, width], un-scaled) = gradient of the SUM over b with respect to the token embeddings, so every sequence receives exactly
- * the gradient of its own loss.  cos_out [n_seq] (device, may be NULL).  Option normalize_fare must be off. */
-int leaf_cosine_input_grad(leaf_text_t h, const float* params, const void* w16_bwd, const int32_t* tokens,
-                           const int32_t* seq_lens, const int32_t* cu_rows, int n_seq, const float* feat,
-                           const float* target, float loss_weight, const void* stash, float* d_embed,
-                           float* cos_out /* [n_seq] */, void* ws, size_t ws_bytes, leaf_stream_t s);
 /* Vocabulary projection (nn_project, optim_utils.py:26-55; leaf_amd/csrc/nnproj.hip): ids[m] = arg-max over v of
  * (q[m] . table[v]) * inv_norm[v], cos[m] (may be NULL) = that value / ||q[m]||.  q [M, d], table [V, d], inv_norm [V] (from
  * leaf_vocab_inv_norms: 1 / ||table[v]||, computed once while the weights are frozen), all fp32 on the device; any M >= 1, V >= 1,
@@ -245,37 +220,37 @@ int leaf_nn_project(const float* q, int M, const float* table, const float* inv_
 int leaf_pgd_step(float* delta, const float* grad, const int32_t* cu_rows, int n_seq, int ctx, int width, float alpha,
                   float eps, int norm, leaf_stream_t s);
 
-/* TextFARE loss + backward (utils_AT.py:321-337): loss = mean_b sum_j (anchor - feat)^2; back-propagates
- * loss * accum_scale (= 1/accum_freq) and ACCUMULATES (+=) into grads (flat fp32, parameter layout).
- * loss_out: one device float (unscaled loss). */
-int leaf_textfare_backward(leaf_text_t h, const float* params, const void* w16_bwd, const int32_t* tokens,
-                           const int32_t* seq_lens, const int32_t* cu_rows, int n_seq, const float* feat,
-                           const float* anchor, float accum_scale, const void* stash, float* grads, float* loss_out,
-                           void* ws, size_t ws_bytes, leaf_stream_t s);
-
-/* the same backward, recording completion events for the overlap of the data-parallel gradient reduction with the backward
- * (SURVEY.md 8e): layer_events = L + 1 hipEvent_t (NULL entries skipped); [l] is recorded on `s` once every gradient of
- * transformer block l is final in `grads` (blocks finish in the order L-1 .. 0), [L] after the last kernel. */
-int leaf_textfare_backward_events(leaf_text_t h, const float* params, const void* w16_bwd, const int32_t* tokens,
-                                  const int32_t* seq_lens, const int32_t* cu_rows, int n_seq, const float* feat,
-                                  const float* anchor, float accum_scale, const void* stash, float* grads, float* loss_out,
-                                  void* ws, size_t ws_bytes, leaf_stream_t s, void* const* layer_events);
-
-/* Backward from ANY upstream gradient: the caller computed a loss of the features that the last training forward returned (feat,
- * fp32 [n_seq, embed_dim]) and hands over dfeat = d loss / d feat (fp32 [n_seq, embed_dim], device).  Back-propagates scale * dfeat
- * through the stash of that forward -- through F.normalize as well when option normalize_fare is on (feat is then the normalised
- * rows; it is read for that product only).  grads (flat fp32, parameter layout; may be NULL): the parameter gradients are
- * ACCUMULATED (+=), as everywhere else.  d_embed (fp32 [rows, width], packed like the activations; may be NULL): OVERWRITTEN with the
- * gradient with respect to the token embeddings / delta.  Both may be given (one pass); giving neither, or a NULL dfeat, is an error
- * reported before any HIP call.  With a scaler state attached and grads given, the fp16 gradient path checks its 16-bit tensors for
- * saturation and poisons gradient element 0, exactly as the TextFARE backward does (GRADIENT SCALER below); a non-finite dfeat
- * reaches the gradients as NaN and the guarded optimizer step skips.  layer_events: NULL, or L + 1 events as in
- * leaf_textfare_backward_events.  Every kernel behind the head is the one the TextFARE and cosine backwards run: fed the dout of
- * those heads (kernel hooks leaf_op_fare_loss / leaf_op_cosine_head) and scale = 1, it writes their gradients bit for bit. */
-int leaf_text_backward(leaf_text_t h, const float* params, const void* w16_bwd, const int32_t* tokens, const int32_t* seq_lens,
-                       const int32_t* cu_rows, int n_seq, const float* feat, const float* dfeat, float scale, const void* stash,
-                       float* grads /* may be NULL */, float* d_embed /* may be NULL */, void* ws, size_t ws_bytes, leaf_stream_t s,
-                       void* const* layer_events /* may be NULL */);
+/* The backward through the stash of the last training forward (feat fp32 [n_seq, embed_dim] = what it returned), from one of three
+ * loss heads; `size` = sizeof(leaf_backward_args), checked.  grads (flat fp32, parameter layout): the parameter gradients are
+ * ACCUMULATED (+=).  d_embed (fp32 [rows, width], packed like the activations): OVERWRITTEN with the un-scaled gradient with respect to
+ * the token embeddings / delta, no parameter gradient touched when grads is NULL.  layer_events (may be NULL), for the overlap of the
+ * data-parallel gradient reduction with the backward: L + 1 hipEvent_t (NULL entries skipped); [l] is recorded on
+ * `stream` once every gradient of transformer block l is final in `grads` (blocks finish in the order L-1 .. 0), [L] after the last
+ * kernel.  Every refusal below is reported before any HIP call.
+ * LEAF_HEAD_FARE: TextFARE (utils_AT.py:321-337), ref = anchor: loss = mean_b sum_j (anchor - feat)^2 into head_out (one device
+ *   float, unscaled); back-propagates loss * scale (= 1/accum_freq).  Exactly one of grads / d_embed; with d_embed (the backward of
+ *   the continuous attack loop, utils_attacks.py:683-692) scale must be 1.
+ * LEAF_HEAD_COSINE: text embedding inversion (optim_utils.py:191-196 with prompt_bs = batch_size = 1, for n_seq independent inversions
+ *   at once), ref = target: loss_b = scale (1 - cos(feat_b, target_b)), the target normalised inside the head, fp32; d_embed = gradient
+ *   of the SUM over b, so every sequence receives exactly the gradient of its own loss.  head_out = cos [n_seq] (may be NULL).
+ *   d_embed only; option normalize_fare must be off.
+ * LEAF_HEAD_UPSTREAM: ANY loss of the features that the caller computed, ref = dfeat = d loss / d feat (fp32 [n_seq, embed_dim],
+ *   device); head_out unused.  Back-propagates scale * dfeat -- through F.normalize as well when option normalize_fare is on (feat is
+ *   then the normalised rows; it is read for that product only).  grads, d_embed or both (one pass).  With a scaler state attached and
+ *   grads given, the fp16 gradient path checks its 16-bit tensors for saturation and poisons gradient element 0, exactly as the
+ *   TextFARE head does (GRADIENT SCALER below); a non-finite dfeat reaches the gradients as NaN and the guarded optimizer step skips.
+ *   Every kernel behind the head is the one the other two heads run: fed their dout (kernel hooks leaf_op_fare_loss /
+ *   leaf_op_cosine_head) and scale = 1, it writes their gradients bit for bit. */
+enum { LEAF_HEAD_FARE = 0, LEAF_HEAD_COSINE = 1, LEAF_HEAD_UPSTREAM = 2 };
+typedef struct leaf_backward_args {
+    uint32_t size;
+    const float* params; const void* w16_bwd;
+    const int32_t *tokens, *seq_lens /* HOST */, *cu_rows; int32_t n_seq;
+    const float* feat; int32_t head; const float* ref; float scale; float* head_out;             /* loss head */
+    const void* stash; float *grads, *d_embed; void* const* layer_events;
+    void* ws; size_t ws_bytes; leaf_stream_t stream;
+} leaf_backward_args;
+int leaf_text_backward(leaf_text_t h, const leaf_backward_args* a);
 
 /* torch.optim.AdamW step over the flat buffers (train_AT_text_only.py:326-341): decoupled weight decay `wd`
  * on the first n_decay elements, 0 on the rest; step counts from 1; grads are multiplied by grad_scale first
@@ -306,7 +281,7 @@ enum {
     LEAF_SC_BC1 = 9, LEAF_SC_SQRT_BC2 = 10, /* bias corrections of the last applied step */
     LEAF_SC_WORDS = 16
 };
-/* attach (or detach with NULL) the scaler state used by leaf_textfare_backward* and leaf_text_backward of this handle */
+/* attach (or detach with NULL) the scaler state used by leaf_text_backward of this handle */
 int leaf_text_set_grad_scaler(leaf_text_t h, float* state);
 
 /* the same step preceded by torch.nn.utils.clip_grad_norm_(parameters, max_norm, 2.0) (--grad-clip-norm,
@@ -355,7 +330,6 @@ int leaf_tok_mutate_encode(leaf_tok_t tk, const char* const* sentences, const in
 typedef struct leaf_dict* leaf_dict_t;
 int leaf_dict_create(const char* words, size_t len, leaf_dict_t* out);
 void leaf_dict_destroy(leaf_dict_t d);
-int64_t leaf_dict_size(leaf_dict_t d);
 int leaf_tok_constrain(leaf_dict_t d, int tokenizer_kind, const char* const* sentences, const int32_t* sent_len, int B,
                        const int32_t* z, const int32_t* c, int rho, uint8_t* valid, uint8_t* fallback, int n_threads);
 /* the same with the caller's SENTENCE SEGMENTATION (tokenizer_kind 1 only): nltk.word_tokenize tokenises sentence by sentence, and
@@ -401,11 +375,10 @@ int leaf_tok_word_tokens(int tokenizer_kind, const char* text, int len, char* ou
 int leaf_tok_duplicate_map(const int32_t* tokens, int B, int rho, int ctx, int32_t* dup_of, int n_threads);
 
 /* ---- per-launch GEMM timing (bench.py roofline): between begin/end every GEMM launch is bracketed by HIP events on
- * its stream; end() sums duration / algorithmic FLOPs / algorithmic bytes / launches per key = kernel_family*16 + operand_dtype*8 + epilogue id
+ * its stream; end_shapes() sums duration / algorithmic FLOPs / algorithmic bytes / launches per key = kernel_family*16 + operand_dtype*8 + epilogue id
  * (family 0 = gemm_nt_kernel, 4 = gemm_nt256_half_kernel, 6 = gemm_nt64_ring_kernel; keys < 128). */
 int leaf_prof_begin(void);
 int leaf_prof_pause(int paused);   /* suspend / resume the recording (per-launch events on a sample of the timed steps only) */
-int leaf_prof_end(double* ms, double* flops, double* bytes /* algorithmic, may be NULL */, int64_t* count, int n_keys);
 /* same records grouped by (key, N, K): info[4 i] = {key, N, K, launches}, rows[i] = sum of M; *n_out groups written */
 int leaf_prof_end_shapes(double* ms, double* flops, double* bytes, int64_t* rows, int32_t* info, int max_groups, int* n_out);
 
@@ -444,16 +417,16 @@ int leaf_op_gemm_lnfold(int dtype, int act, const void* A, const void* Bp, void*
  * softmax(q k^T / 8 + causal mask) v, src/open_clip/transformer.py:225,239-252): out[rows, width] (eot_pos: [n_seq, width]) from the
  * 16-bit residual copy x16 [rows, width], Wp = 16-bit(gamma * in_proj_weight) [3 width, width] with its c / s vectors and the rows'
  * (mean, rstd).  lens (HOST) = rows per sequence, cu (device) their exclusive prefix sum; prefix / base_cu / kv (device, or all
- * NULL) = cached-prefix mode as in leaf_score_candidates_prefix with candidates grouped `group` per caption; tile_seq = device
+ * NULL) = cached-prefix mode as in leaf_score_pass with candidates grouped `group` per caption; tile_seq = device
  * scratch [2 (n_seq + 1)].  Kernel hook for tools/qkv_attn_bench.py; the scoring passes call the same launch internally. */
 int leaf_op_qkv_attn(int dtype, const void* x16, const void* Wp, const float* c_vec, const float* s_vec, const void* rowstat,
                      void* out, const void* kv, const int32_t* lens, const int32_t* cu, const int32_t* prefix,
                      const int32_t* base_cu, const int32_t* eot_pos, int32_t* tile_seq, int n_seq, int rows, int group,
                      int ctx, int heads, int width, leaf_stream_t s);
-/* the classification score of leaf_score_candidates_cls alone, on given feature rows feat [B*rho, D] (kernel hook for the tests) */
+/* the classification score of leaf_score_pass alone, on given feature rows feat [B*rho, D] (kernel hook for the tests) */
 int leaf_op_classify(const float* feat, const float* class_feat, const int32_t* labels, int B, int rho, int D, int C, float* loss,
                      int32_t* pred, float* logits, int32_t* best_idx, float* best_feat, leaf_stream_t s);
-/* the cosine head of leaf_cosine_input_grad alone (kernel hook for the tests): dout [B, D] = d (sum_b loss_b) / d feat, cos_out [B]
+/* the cosine head of leaf_text_backward (LEAF_HEAD_COSINE) alone (kernel hook for the tests): dout [B, D] = d (sum_b loss_b) / d feat, cos_out [B]
  * (may be NULL); ws: 64 + 2 B device floats */
 int leaf_op_cosine_head(const float* feat, const float* target, int B, int D, float loss_weight, float* dout, float* cos_out,
                         float* ws, leaf_stream_t s);
@@ -472,9 +445,7 @@ int leaf_op_attention_fwd_map(const void* qkv, const void* kv, void* out, const 
                               int max_len, int single_edit, int heads, int width, int dtype, leaf_stream_t s);
 int leaf_op_layernorm(const float* x, const float* g, const float* b, float eps, void* out16, int rows, int width,
                       int dtype, leaf_stream_t s);
-int leaf_op_attention_bwd(const void* qkv, int qkv_dtype, const void* dout_bf16, void* dqkv_bf16, int n_seq, int ctx,
-                          int heads, int width, leaf_stream_t s);
-/* attention backward with an explicit gradient dtype (LEAF_DTYPE_*) for dout / dqkv */
+/* attention backward; g_dtype (LEAF_DTYPE_*) is the gradient type of dout / dqkv */
 int leaf_op_attention_bwd_t(const void* qkv, int qkv_dtype, const void* dout16, void* dqkv16, int g_dtype, int n_seq,
                             int ctx, int heads, int width, leaf_stream_t s);
 /* the same on the row map of the training backward: cu [n_seq + 1] on the device = packed rows, NULL = dense (ctx rows per sequence) */

@@ -15,12 +15,44 @@ class TextCfgC(C.Structure):
                 ("ln_eps", C.c_float)]
 
 
+# the argument structs of the three pass entries (include/leaf_hip.h: same field names, order and types; tests/test_abi_structs_cpu.py
+# holds them to the header).  Every pointer is a c_void_p: assign an address (``tensor.data_ptr()``, ``array.ctypes.data``) or None.
+# A struct keeps no tensor alive: whoever fills one owns the buffers behind its addresses until the call has returned.
+_P, _I, _Z = C.c_void_p, C.c_int32, C.c_size_t
+
+
+class _Args(C.Structure):
+    def __init__(self, **fields):
+        super().__init__(size=C.sizeof(self), **fields)
+
+
+class ScoreArgs(_Args):
+    _fields_ = [("size", C.c_uint32), ("params", _P), ("w16_fwd", _P), ("tokens", _P), ("seq_lens", _P), ("cu_rows", _P),
+                ("prefix", _P), ("base_cu", _P), ("kv", _P), ("base_rows", _Z), ("kv_bytes", _Z), ("max_len", _I), ("kv_write", _I),
+                ("B", _I), ("rho", _I), ("anchor", _P), ("objective", _I),
+                ("class_feat", _P), ("C", _I), ("labels", _P), ("pred", _P), ("logits", _P),
+                ("best_idx", _P), ("best_feat", _P), ("loss", _P), ("ws", _P), ("ws_bytes", _Z), ("stream", _P)]
+
+
+class TrainFwdArgs(_Args):
+    _fields_ = [("size", C.c_uint32), ("params", _P), ("w16_fwd", _P), ("tokens", _P), ("seq_lens", _P), ("cu_rows", _P), ("n_seq", _I),
+                ("delta", _P), ("pool_last", _I), ("out", _P), ("stash", _P), ("stash_bytes", _Z),
+                ("ws", _P), ("ws_bytes", _Z), ("stream", _P)]
+
+
+class BackwardArgs(_Args):
+    _fields_ = [("size", C.c_uint32), ("params", _P), ("w16_bwd", _P), ("tokens", _P), ("seq_lens", _P), ("cu_rows", _P), ("n_seq", _I),
+                ("feat", _P), ("head", _I), ("ref", _P), ("scale", C.c_float), ("head_out", _P),
+                ("stash", _P), ("grads", _P), ("d_embed", _P), ("layer_events", _P), ("ws", _P), ("ws_bytes", _Z), ("stream", _P)]
+
+
+HEAD_FARE, HEAD_COSINE, HEAD_UPSTREAM = range(3)      # LEAF_HEAD_*
+
 _SIGS = {
     "leaf_last_error": (C.c_char_p, []),
     "leaf_version": (C.c_int, []),
     "leaf_text_create": (C.c_int, [C.POINTER(TextCfgC), C.c_int, C.POINTER(C.c_void_p)]),
     "leaf_text_destroy": (None, [C.c_void_p]),
-    "leaf_text_set_chunk": (C.c_int, [C.c_void_p, C.c_int]),
     "leaf_text_set_option": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int]),
     "leaf_text_get_option": (C.c_int, [C.c_void_p, C.c_char_p]),
     "leaf_text_set_grad_scaler": (C.c_int, [C.c_void_p, C.c_void_p]),
@@ -38,41 +70,12 @@ _SIGS = {
     "leaf_text_precise_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int]),
     "leaf_text_forward_precise": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
                                             C.c_void_p, C.c_size_t, C.c_void_p]),
-    "leaf_score_candidates": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                        C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
-                                        C.c_void_p, C.c_size_t, C.c_void_p]),
-    "leaf_score_candidates_cls": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                            C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
-                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "leaf_score_pass": (C.c_int, [C.c_void_p, C.POINTER(ScoreArgs)]),
     "leaf_select_topk": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                    C.c_void_p]),
     "leaf_text_kv_bytes": (C.c_size_t, [C.c_void_p, C.c_int]),
     "leaf_text_forward_kv": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                        C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]),
-    "leaf_score_candidates_prefix": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p,
-                                               C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
-                                               C.c_void_p, C.c_size_t, C.c_void_p]),
-    "leaf_score_candidates_prefix_cls": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p,
-                                                   C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
-                                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
-    "leaf_score_candidates_prefix_fused": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                                     C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
-                                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
-                                                     C.c_void_p]),
-    "leaf_text_forward_train_delta": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                                C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
-                                                C.c_size_t, C.c_void_p]),
-    "leaf_textfare_input_grad": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
-                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                           C.c_size_t, C.c_void_p]),
-    "leaf_text_forward_train_last": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                               C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
-                                               C.c_void_p]),
-    "leaf_cosine_input_grad": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
-                                         C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                         C.c_size_t, C.c_void_p]),
     "leaf_vocab_inv_norms": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "leaf_nn_project_ws_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "leaf_nn_project": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
@@ -81,18 +84,8 @@ _SIGS = {
                                       C.c_void_p]),
     "leaf_pgd_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float,
                                C.c_int, C.c_void_p]),
-    "leaf_text_forward_train": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                          C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
-                                          C.c_void_p]),
-    "leaf_textfare_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                         C.c_int, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p,
-                                         C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
-    "leaf_textfare_backward_events": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                                C.c_int, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p,
-                                                C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
-    "leaf_text_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
-                                     C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
-                                     C.c_void_p]),
+    "leaf_text_forward_train": (C.c_int, [C.c_void_p, C.POINTER(TrainFwdArgs)]),
+    "leaf_text_backward": (C.c_int, [C.c_void_p, C.POINTER(BackwardArgs)]),
     "leaf_clip_grads_inplace": (C.c_int, [C.c_void_p, C.c_size_t, C.c_float, C.c_float, C.c_void_p, C.c_void_p]),
     "leaf_adamw_step_clip": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_float,
                                       C.c_float, C.c_float, C.c_float, C.c_float, C.c_int, C.c_float, C.c_float,
@@ -100,7 +93,6 @@ _SIGS = {
     "leaf_adamw_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_float,
                                   C.c_float, C.c_float, C.c_float, C.c_float, C.c_int, C.c_float, C.c_void_p]),
     "leaf_text_split_bytes": (C.c_size_t, [C.c_void_p, C.c_int]),
-    "leaf_text_split_pack": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "leaf_text_split_pack_masks": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "leaf_tok_create": (C.c_int, [C.c_char_p, C.c_size_t, C.POINTER(C.c_void_p)]),
     "leaf_tok_destroy": (None, [C.c_void_p]),
@@ -110,7 +102,6 @@ _SIGS = {
                                          C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
     "leaf_dict_create": (C.c_int, [C.c_char_p, C.c_size_t, C.POINTER(C.c_void_p)]),
     "leaf_dict_destroy": (None, [C.c_void_p]),
-    "leaf_dict_size": (C.c_int64, [C.c_void_p]),
     "leaf_tok_constrain_ranges": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_char_p), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
     "leaf_punkt_create": (C.c_int, [C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t,
@@ -127,8 +118,6 @@ _SIGS = {
                                      C.c_void_p, C.c_void_p, C.c_int]),
     "leaf_prof_begin": (C.c_int, []),
     "leaf_prof_pause": (C.c_int, [C.c_int]),
-    "leaf_prof_end": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int64),
-                               C.c_int]),
     "leaf_prof_end_shapes": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int64),
                                       C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_int)]),
     "leaf_op_gemm": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
@@ -168,8 +157,6 @@ _SIGS = {
                                        C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
     "leaf_op_project_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p,
                                       C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
-    "leaf_op_attention_bwd": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
-                                        C.c_void_p]),
 }
 
 # gradient-scaler state layout (include/leaf_hip.h LEAF_SC_*)

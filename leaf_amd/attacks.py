@@ -11,7 +11,7 @@ produced (checked against traces of the reference in tests/golden/attack_trace.j
 * ``attack_text_leaf`` / ``attack_text`` utils_attacks.py:297-393,646-647
 
 Difference by design: the reference computes ``encode_text`` -> loss -> ``argmax`` as separate torch ops;
-here one C-ABI call (``leaf_score_candidates``) runs the forward of all B*rho candidates, the loss, the
+here one C-ABI call (``leaf_score_pass``) runs the forward of all B*rho candidates, the loss, the
 first-index arg-max and the winner gather on the GPU and only B indices come back to the host.
 """
 from __future__ import annotations

@@ -22,7 +22,7 @@ int leaf_check(hipError_t e, const char* what) {
 }
 
 extern "C" const char* leaf_last_error(void) { return g_err; }
-extern "C" int leaf_version(void) { return 1; }
+extern "C" int leaf_version(void) { return 2; }
 
 // ------------------------------------------------------------------ options (include/leaf_hip.h leaf_text_set_option)
 namespace {
@@ -35,14 +35,14 @@ struct Option {
     int (*norm)(const leaf_text*, int);     // stored value of a requested one; null: not set through the table
 };
 const Option OPTIONS[] = {
-    {"chunk", &leaf_text::chunk, nullptr, nullptr},                 // set: leaf_text_set_chunk
+    {"chunk", &leaf_text::chunk, nullptr, nullptr},                 // set: leaf_text_set_option itself (range check)
     {"last_layer_trim", &leaf_text::last_trim, "LEAF_LAST_TRIM", norm_flag},
     {"normalize_fare", &leaf_text::normalize_fare, nullptr, norm_flag},
     {"ln_fold", &leaf_text::ln_fold, "LEAF_LN_FOLD", norm_ln_fold},
     {"fuse_attn", &leaf_text::fuse_attn, "LEAF_FUSE_ATTN", norm_flag},
     {"compact_resid", &leaf_text::compact_resid, "LEAF_COMPACT_RESID", norm_flag},
     {"single_edit", &leaf_text::single_edit, nullptr, norm_flag},
-    {"split_blocks", &leaf_text::split_blocks, nullptr, nullptr},   // get only: leaf_text_split_pack sets it
+    {"split_blocks", &leaf_text::split_blocks, nullptr, nullptr},   // get only: leaf_text_split_pack_masks sets it
 };
 const Option* find_option(const char* name) {
     for (const Option& o : OPTIONS)
@@ -120,19 +120,17 @@ extern "C" void leaf_text_destroy(leaf_text_t h) {
     delete h;
 }
 
-extern "C" int leaf_text_set_chunk(leaf_text_t h, int seqs) {
-    if (!h || seqs < 1) { leaf_set_error("bad chunk"); return 1; }
-    h->chunk = seqs;
-    return 0;
-}
-
 extern "C" int leaf_text_set_option(leaf_text_t h, const char* name, int value) {
     if (!h || !name) { leaf_set_error("null argument"); return 1; }
-    if (!strcmp(name, "chunk")) return leaf_text_set_chunk(h, value);
+    if (!strcmp(name, "chunk")) {
+        if (value < 1) { leaf_set_error("bad chunk"); return 1; }
+        h->chunk = value;
+        return 0;
+    }
     const Option* o = find_option(name);
     if (!o || !o->norm) { leaf_set_error("unknown option '%s'", name); return 1; }
     const int v = o->norm(h, value);
-    if (o->member == &leaf_text::ln_fold && !v && h->split_blocks) { leaf_set_error("ln_fold = 0 with split blocks active: the split GEMMs are LN-folded (leaf_text_split_pack(.., 0, ..) first)"); return 1; }
+    if (o->member == &leaf_text::ln_fold && !v && h->split_blocks) { leaf_set_error("ln_fold = 0 with split blocks active: the split GEMMs are LN-folded (leaf_text_split_pack_masks(.., 0, ..) first)"); return 1; }
     h->*o->member = v;
     return 0;
 }
@@ -164,8 +162,8 @@ extern "C" int leaf_text_split_pack_masks(leaf_text_t h, const float* params, co
     if (!h) { leaf_set_error("null handle"); return 1; }
     if (blocks == 0) { h->split_blocks = 0; h->split_buf = nullptr; return 0; }
     if (blocks < 0 || blocks > h->cfg.layers - 1 || blocks > 64) { leaf_set_error("split blocks %d out of range 0..%d", blocks, h->cfg.layers - 1); return 1; }
-    if (!params || !buf || !masks) { leaf_set_error("leaf_text_split_pack: params / masks / buf is null"); return 1; }
-    if (!h->ln_fold) { leaf_set_error("leaf_text_split_pack: the split GEMMs exist in the LN-folded forward only (option ln_fold is 0)"); return 1; }
+    if (!params || !buf || !masks) { leaf_set_error("leaf_text_split_pack_masks: params / masks / buf is null"); return 1; }
+    if (!h->ln_fold) { leaf_set_error("leaf_text_split_pack_masks: the split GEMMs exist in the LN-folded forward only (option ln_fold is 0)"); return 1; }
     for (int l = 0; l < blocks; ++l)
         if (masks[l] < 0 || masks[l] > 15) { leaf_set_error("split mask %d of block %d: bits 0..3 (QKV, out_proj, c_fc, c_proj)", masks[l], l); return 1; }
     hipStream_t s = (hipStream_t)s_;
@@ -181,12 +179,6 @@ extern "C" int leaf_text_split_pack_masks(leaf_text_t h, const float* params, co
         if (h->split_proj(l)) LEAF_TRY(leaf_launch_split_pack(params + o.proj_w, nullptr, (void*)h->split_proj_lo(l), nullptr, d, 4 * d, 0, dt, s));
     }
     return 0;
-}
-
-extern "C" int leaf_text_split_pack(leaf_text_t h, const float* params, int blocks, void* buf, leaf_stream_t s) {
-    int32_t masks[64];
-    for (int l = 0; l < 64; ++l) masks[l] = 15;
-    return leaf_text_split_pack_masks(h, params, masks, blocks, buf, s);
 }
 
 extern "C" int leaf_text_pack_weights(leaf_text_t h, const float* params, void* w16_fwd, void* w16_bwd,
@@ -306,17 +298,9 @@ extern "C" int leaf_prof_pause(int paused) {
     return 0;
 }
 
-// Stops recording, waits for the recorded events and sums per key (= LEAF_PROF_KEY: kernel_family*32 + dtype*16 + epilogue id, < 512):
-// ms[key], flops[key], bytes[key] (algorithmic operand + output bytes, may be null), count[key].
-extern "C" int leaf_prof_end(double* ms, double* flops, double* bytes, int64_t* count, int n_keys) {
-    for (int i = 0; i < n_keys; ++i) { ms[i] = 0; flops[i] = 0; count[i] = 0; if (bytes) bytes[i] = 0; }
-    return prof_drain([&](const ProfRec& r, float t) {
-        if (r.key >= 0 && r.key < n_keys) { ms[r.key] += t; flops[r.key] += r.flops; count[r.key] += 1; if (bytes) bytes[r.key] += r.bytes; }
-    });
-}
-
-// Same as leaf_prof_end but grouped by (key, N, K) -- one line per GEMM SHAPE of each kernel, so that e.g. the two
-// residual GEMMs (out_proj: N = K = d, HBM-bound; c_proj: K = 4d, MFMA-bound) are reported separately.  info[i] =
+// Stops recording, waits for the recorded events and sums them grouped by (key = LEAF_PROF_KEY: kernel_family*32 + dtype*16 +
+// epilogue id, N, K) -- one line per GEMM SHAPE of each kernel, so that e.g. the two residual GEMMs (out_proj: N = K = d, HBM-bound;
+// c_proj: K = 4d, MFMA-bound) are reported separately.  ms / flops / bytes (algorithmic operand + output bytes) per group; info[i] =
 // {key (+ LEAF_PROF_BIG = 1024 for launches of >= 16,384 rows), N, K, launches}; rows[i] = sum of M over the launches.  Returns the number of groups in *n_out (<= max_groups).
 extern "C" int leaf_prof_end_shapes(double* ms, double* flops, double* bytes, int64_t* rows, int32_t* info, int max_groups,
                                     int* n_out) {
@@ -360,34 +344,7 @@ extern "C" int leaf_text_forward(leaf_text_t h, const float* params, const void*
 
 // ------------------------------------------------------------------ scoring passes
 namespace {
-// argument checks common to the three scoring entry points (extra_ok: the entry's own pointers are there)
-int score_check(bool extra_ok, leaf_text_t h, const float* params, const void* w16_fwd, const int32_t* tokens, const float* anchor,
-                const int32_t* best_idx, const void* ws, int B, int rho, int objective) {
-    if (!extra_ok || !h || !params || !w16_fwd || !tokens || !anchor || !best_idx || !ws || B < 1 || rho < 1) {
-        leaf_set_error("null/invalid argument");
-        return 1;
-    }
-    if (objective < 0 || objective > 3) { leaf_set_error("unknown objective %d", objective); return 1; }
-    return 0;
-}
-// what a scoring pass compares its candidates with: one anchor row per caption under one of the four objectives (leaf_launch_score),
-// or a class matrix shared by all captions with a label per caption (leaf_launch_classify, classify.hip)
-struct ScoreTarget {
-    const float* anchor = nullptr;       // [B, D]
-    int objective = 0;
-    const float* class_feat = nullptr;   // [C, D], unit rows; non-null selects the classification margin loss
-    int C = 0;
-    const int32_t* labels = nullptr;     // [B], device
-    int32_t* pred = nullptr;             // [B, rho] or null
-    float* logits = nullptr;             // [B * rho, C] or null
-};
-ScoreTarget anchor_target(const float* anchor, int objective) {
-    ScoreTarget t;
-    t.anchor = anchor;
-    t.objective = objective;
-    return t;
-}
-// argument checks of the two classification entries on top of score_check's (loss is required: best_idx is taken from it)
+// argument checks of the class target (loss is required: best_idx is taken from it)
 int cls_check(const float* class_feat, int C, const int32_t* labels, const float* loss, int rho) {
     if (!class_feat || !labels || !loss) { leaf_set_error("null/invalid argument"); return 1; }
     if (C < LEAF_CLS_MIN_CLASSES || C > LEAF_CLS_MAX_CLASSES) {
@@ -397,53 +354,7 @@ int cls_check(const float* class_feat, int C, const int32_t* labels, const float
     if (rho > LEAF_SCORE_MAX_RHO) { leaf_set_error("rho %d: one scoring launch takes %d candidates per caption", rho, LEAF_SCORE_MAX_RHO); return 1; }
     return 0;
 }
-ScoreTarget class_target(const float* class_feat, int C, const int32_t* labels, int32_t* pred, float* logits) {
-    ScoreTarget t;
-    t.class_feat = class_feat;
-    t.C = C;
-    t.labels = labels;
-    t.pred = pred;
-    t.logits = logits;
-    return t;
-}
-// features of the pass's n_seq sequences -> workspace, then the best of the rho candidates of each of the B captions: the candidates
-// are the LAST B * rho sequences of the pass (the fused first stage has its B captions in front of them)
-int score_pass(leaf_text_t h, const float* params, const void* w16_fwd, const int32_t* tokens, const int32_t* lens, const int32_t* cu,
-               int n_seq, const PrefixPlan& pp, const ScoreTarget& tg, int B, int rho, int32_t* best_idx, float* best_feat,
-               float* loss, void* ws, size_t ws_bytes, hipStream_t s) {
-    const int D = h->cfg.embed_dim;
-    Carver c(ws, ws_bytes);
-    float* feat = (float*)c.take((size_t)n_seq * D * 4);
-    const int normalize = (tg.class_feat || tg.objective == LEAF_OBJ_SIM || tg.objective == LEAF_OBJ_DISSIM);
-    const int rc = forward_all(h, params, w16_fwd, tokens, lens, cu, n_seq, feat, normalize, c, s, pp);
-    if (rc) return rc;
-    const float* cand = feat + (size_t)(n_seq - B * rho) * D;
-    if (tg.class_feat)
-        LEAF_TRY(leaf_launch_classify(cand, tg.class_feat, tg.labels, B, rho, D, tg.C, loss, tg.pred, tg.logits, best_idx, best_feat, s));
-    else
-        LEAF_TRY(leaf_launch_score(cand, tg.anchor, B, rho, D, tg.objective, best_idx, best_feat, loss, s));
-    return 0;
-}
 }  // namespace
-
-extern "C" int leaf_score_candidates(leaf_text_t h, const float* params, const void* w16_fwd, const int32_t* tokens,
-                                     const int32_t* seq_lens, const int32_t* cu_rows, const float* anchor, int B,
-                                     int rho, int objective, int32_t* best_idx,
-                                     float* best_feat, float* loss, void* ws, size_t ws_bytes, leaf_stream_t s) {
-    if (score_check(true, h, params, w16_fwd, tokens, anchor, best_idx, ws, B, rho, objective)) return 1;
-    return score_pass(h, params, w16_fwd, tokens, seq_lens, cu_rows, B * rho, PrefixPlan(), anchor_target(anchor, objective), B, rho, best_idx, best_feat,
-                      loss, ws, ws_bytes, (hipStream_t)s);
-}
-
-// the same pass scored against a class matrix (classify.hip); score_check's anchor slot carries the class matrix, objective 0 is unused
-extern "C" int leaf_score_candidates_cls(leaf_text_t h, const float* params, const void* w16_fwd, const int32_t* tokens,
-                                         const int32_t* seq_lens, const int32_t* cu_rows, const float* class_feat, int C,
-                                         const int32_t* labels, int B, int rho, int32_t* best_idx, float* best_feat, float* loss,
-                                         int32_t* pred, float* logits, void* ws, size_t ws_bytes, leaf_stream_t s) {
-    if (score_check(true, h, params, w16_fwd, tokens, class_feat, best_idx, ws, B, rho, 0) || cls_check(class_feat, C, labels, loss, rho)) return 1;
-    return score_pass(h, params, w16_fwd, tokens, seq_lens, cu_rows, B * rho, PrefixPlan(), class_target(class_feat, C, labels, pred, logits),
-                      B, rho, best_idx, best_feat, loss, ws, ws_bytes, (hipStream_t)s);
-}
 
 // ------------------------------------------------------------------ prefix reuse
 extern "C" size_t leaf_text_kv_bytes(leaf_text_t h, int n_seq) {
@@ -478,66 +389,66 @@ extern "C" int leaf_text_forward_kv(leaf_text_t h, const float* params, const vo
                          (hipStream_t)s, kvp, max_len);
 }
 
-// the prefix map of a leaf_score_candidates_prefix* pass: candidates grouped rho per caption, earlier positions read from `kv`
-static PrefixPlan prefix_plan(leaf_text_t h, const int32_t* prefix, const int32_t* base_cu, const void* kv, size_t base_rows, int max_len,
-                              int rho) {
-    PrefixPlan pp;
-    pp.prefix_dev = prefix;
-    pp.base_cu_dev = base_cu;
-    pp.max_len = max_len;
-    pp.kv = (const uint16_t*)kv;
-    pp.kv_stride = base_rows * 3 * h->cfg.width;
-    pp.group = rho;
-    return pp;
-}
-extern "C" int leaf_score_candidates_prefix(leaf_text_t h, const float* params, const void* w16_fwd, const int32_t* tokens,
-                                            const int32_t* suffix_lens, const int32_t* cu_suffix, const int32_t* prefix,
-                                            const int32_t* base_cu, const void* kv, size_t base_rows, int max_len,
-                                            const float* anchor, int B, int rho, int objective, int32_t* best_idx, float* best_feat, float* loss,
-                                            void* ws, size_t ws_bytes, leaf_stream_t s) {
-    if (score_check(suffix_lens && cu_suffix && prefix && base_cu && kv, h, params, w16_fwd, tokens, anchor, best_idx, ws, B, rho, objective))
+// One scoring pass (include/leaf_hip.h, leaf_score_args): the fields say which rows it computes and what it compares the candidates
+// with -- one anchor row per caption under one of the four objectives (leaf_launch_score), or a class matrix shared by all captions
+// with a label per caption (leaf_launch_classify, classify.hip).  Every refusal comes before the first HIP call.
+extern "C" int leaf_score_pass(leaf_text_t h, const leaf_score_args* a) {
+    if (!a || a->size != sizeof(*a)) { leaf_set_error("leaf_score_args: size %u, this library's is %zu", a ? a->size : 0u, sizeof(*a)); return 1; }
+    if (!h || !a->params || !a->w16_fwd || !a->tokens || !a->best_idx || !a->ws || a->B < 1 || a->rho < 1) {
+        leaf_set_error("null/invalid argument");
         return 1;
-    return score_pass(h, params, w16_fwd, tokens, suffix_lens, cu_suffix, B * rho, prefix_plan(h, prefix, base_cu, kv, base_rows, max_len, rho), anchor_target(anchor, objective), B, rho, best_idx, best_feat, loss,
-                      ws, ws_bytes, (hipStream_t)s);
-}
-
-extern "C" int leaf_score_candidates_prefix_cls(leaf_text_t h, const float* params, const void* w16_fwd, const int32_t* tokens,
-                                                const int32_t* suffix_lens, const int32_t* cu_suffix, const int32_t* prefix,
-                                                const int32_t* base_cu, const void* kv, size_t base_rows, int max_len,
-                                                const float* class_feat, int C, const int32_t* labels, int B, int rho,
-                                                int32_t* best_idx, float* best_feat, float* loss, int32_t* pred, float* logits,
-                                                void* ws, size_t ws_bytes, leaf_stream_t s) {
-    if (score_check(suffix_lens && cu_suffix && prefix && base_cu && kv, h, params, w16_fwd, tokens, class_feat, best_idx, ws, B, rho, 0) ||
-        cls_check(class_feat, C, labels, loss, rho))
+    }
+    if ((a->anchor != nullptr) == (a->class_feat != nullptr)) { leaf_set_error("score_pass: exactly one of anchor / class_feat"); return 1; }
+    if (a->anchor && (a->objective < 0 || a->objective > 3)) { leaf_set_error("unknown objective %d", a->objective); return 1; }
+    if (a->class_feat && cls_check(a->class_feat, a->C, a->labels, a->loss, a->rho)) return 1;
+    const bool fused = a->kv_write != 0;
+    if (!a->prefix && (a->kv || a->base_cu || fused)) { leaf_set_error("score_pass: kv / base_cu / kv_write without prefix"); return 1; }
+    if (a->prefix && (!a->kv || !a->seq_lens || !a->cu_rows || (a->base_cu == nullptr) != fused)) {
+        leaf_set_error("score_pass: a prefix pass needs seq_lens, cu_rows, kv and base_cu (the fused first stage: no base_cu)");
         return 1;
-    return score_pass(h, params, w16_fwd, tokens, suffix_lens, cu_suffix, B * rho, prefix_plan(h, prefix, base_cu, kv, base_rows, max_len, rho),
-                      class_target(class_feat, C, labels, pred, logits), B, rho, best_idx, best_feat, loss, ws, ws_bytes, (hipStream_t)s);
-}
-
-// The clean-caption K/V pass and the FIRST stage's scoring in one pass: sequences 0 .. B-1 are the captions (full rows, prefix 0),
-// B .. B + B rho - 1 their candidates; seq_lens (host) / cu_rows / prefix (device) cover all of them.  Returns 2 (and an error
-// text) when the rows do not fit one chunk: the caller then runs leaf_text_forward_kv + leaf_score_candidates_prefix.
-extern "C" int leaf_score_candidates_prefix_fused(leaf_text_t h, const float* params, const void* w16_fwd, const int32_t* tokens,
-                                                  const int32_t* seq_lens, const int32_t* cu_rows, const int32_t* prefix,
-                                                  int max_len, const float* anchor, int B, int rho, int objective,
-                                                  int32_t* best_idx, float* best_feat, float* loss, void* kv, size_t kv_bytes,
-                                                  void* ws, size_t ws_bytes, leaf_stream_t s) {
-    if (score_check(seq_lens && cu_rows && prefix && kv, h, params, w16_fwd, tokens, anchor, best_idx, ws, B, rho, objective)) return 1;
-    size_t base_rows = 0;
-    for (int i = 0; i < B; ++i) base_rows += seq_lens[i];
-    const size_t stride = base_rows * 3 * h->cfg.width;
-    if (stride * 2 * h->cfg.layers > kv_bytes) { leaf_set_error("kv cache too small"); return 1; }
+    }
+    if (fused && a->class_feat) { leaf_set_error("score_pass: the fused first stage takes an anchor target only"); return 1; }
+    // candidates grouped rho per caption; earlier positions are read from the cache ...
     PrefixPlan pp;
-    pp.prefix_dev = prefix;
-    pp.base_cu_dev = cu_rows;          // the captions are the first sequences: their row offsets are the first B entries
-    pp.max_len = max_len;
-    pp.kv_stride = stride;
-    pp.group = rho;
-    pp.group_off = B;
-    pp.kv_copy = (uint16_t*)kv;
-    pp.kv_self_rows = base_rows;
-    return score_pass(h, params, w16_fwd, tokens, seq_lens, cu_rows, B + B * rho, pp, anchor_target(anchor, objective), B, rho, best_idx, best_feat, loss,
-                      ws, ws_bytes, (hipStream_t)s);
+    int n_seq = a->B * a->rho;
+    if (a->prefix) {
+        pp.prefix_dev = a->prefix;
+        pp.max_len = a->max_len;
+        pp.group = a->rho;
+        size_t base_rows = a->base_rows;
+        if (fused) {
+            // ... which this pass writes itself: sequences 0 .. B-1 are the captions (full rows, prefix 0), B .. B + B rho - 1 their
+            // candidates; seq_lens / cu_rows / prefix cover all of them.  forward_all returns 2 (and an error text) when the rows do
+            // not fit one chunk: the caller then runs leaf_text_forward_kv and a prefix pass
+            base_rows = 0;
+            for (int i = 0; i < a->B; ++i) base_rows += a->seq_lens[i];
+            if (base_rows * 3 * h->cfg.width * 2 * h->cfg.layers > a->kv_bytes) { leaf_set_error("kv cache too small"); return 1; }
+            n_seq += a->B;
+            pp.base_cu_dev = a->cu_rows;          // the captions are the first sequences: their row offsets are the first B entries
+            pp.group_off = a->B;
+            pp.kv_copy = (uint16_t*)a->kv;
+            pp.kv_self_rows = base_rows;
+        } else {
+            pp.base_cu_dev = a->base_cu;
+            pp.kv = (const uint16_t*)a->kv;
+        }
+        pp.kv_stride = base_rows * 3 * h->cfg.width;
+    }
+    // features of the pass's n_seq sequences -> workspace, then the best of the rho candidates of each of the B captions: the candidates
+    // are the LAST B * rho sequences of the pass (the fused first stage has its B captions in front of them)
+    const int D = h->cfg.embed_dim, B = a->B, rho = a->rho;
+    hipStream_t s = (hipStream_t)a->stream;
+    Carver c(a->ws, a->ws_bytes);
+    float* feat = (float*)c.take((size_t)n_seq * D * 4);
+    const int normalize = (a->class_feat || a->objective == LEAF_OBJ_SIM || a->objective == LEAF_OBJ_DISSIM);
+    const int rc = forward_all(h, a->params, a->w16_fwd, a->tokens, a->seq_lens, a->cu_rows, n_seq, feat, normalize, c, s, pp);
+    if (rc) return rc;
+    const float* cand = feat + (size_t)(n_seq - B * rho) * D;
+    if (a->class_feat)
+        LEAF_TRY(leaf_launch_classify(cand, a->class_feat, a->labels, B, rho, D, a->C, a->loss, a->pred, a->logits, a->best_idx, a->best_feat, s));
+    else
+        LEAF_TRY(leaf_launch_score(cand, a->anchor, B, rho, D, a->objective, a->best_idx, a->best_feat, a->loss, s));
+    return 0;
 }
 
 // ------------------------------------------------------------------ single-kernel hooks for the parity tests
@@ -594,7 +505,7 @@ extern "C" int leaf_op_gemm_lnfold(int dtype, int act, const void* A, const void
     return leaf_gemm(g, dtype, act < 0 ? EPI_LNFOLD_T : EPI_LNFOLD_ACT_T, (hipStream_t)s);
 }
 // The fused QKV + attention launch alone (tools/qkv_attn_bench.py): lens (host) = rows per sequence, cu / prefix / base_cu device
-// arrays as in leaf_score_candidates_prefix (prefix / base_cu / kv may be null: no cached prefix), tile_seq = device scratch
+// arrays as in a prefix leaf_score_pass (prefix / base_cu / kv may be null: no cached prefix), tile_seq = device scratch
 // [n_seq + 1].  Synchronous plan upload: a measuring / test hook, not a step of the pipeline.
 extern "C" int leaf_op_qkv_attn(int dtype, const void* x16, const void* Wp, const float* c_vec, const float* s_vec, const void* rowstat,
                                 void* out, const void* kv, const int32_t* lens, const int32_t* cu, const int32_t* prefix,
@@ -641,17 +552,12 @@ extern "C" int leaf_op_layernorm(const float* x, const float* g, const float* b,
                                  int width, int dtype, leaf_stream_t s) {
     return leaf_check(leaf_launch_layernorm(x, g, b, eps, out16, rows, width, dtype, (hipStream_t)s), "layernorm");
 }
-extern "C" int leaf_op_attention_bwd(const void* qkv, int qkv_dtype, const void* dout_bf16, void* dqkv_bf16, int n_seq,
-                                     int ctx, int heads, int width, leaf_stream_t s) {
-    return leaf_check(leaf_launch_attention_bwd(qkv, qkv_dtype, dout_bf16, dqkv_bf16, LEAF_BF16, n_seq,
-                                                RowMap{nullptr, 0, 0, ctx, nullptr, nullptr, 1}, heads, width, (hipStream_t)s), "attention_bwd");
-}
 extern "C" int leaf_op_attention_bwd_t(const void* qkv, int qkv_dtype, const void* dout16, void* dqkv16, int g_dtype,
                                        int n_seq, int ctx, int heads, int width, leaf_stream_t s) {
     return leaf_check(leaf_launch_attention_bwd(qkv, qkv_dtype, dout16, dqkv16, g_dtype, n_seq,
                                                 RowMap{nullptr, 0, 0, ctx, nullptr, nullptr, 1}, heads, width, (hipStream_t)s), "attention_bwd");
 }
-// ... and on packed rows (cu [n_seq + 1] on the device, NULL = dense): the RowMap of backward_impl (tests/test_gpu_backward_rows.py)
+// ... and on packed rows (cu [n_seq + 1] on the device, NULL = dense): the RowMap of leaf_text_backward (tests/test_gpu_backward_rows.py)
 extern "C" int leaf_op_attention_bwd_map(const void* qkv, int qkv_dtype, const void* dout16, void* dqkv16, int g_dtype,
                                          const int32_t* cu, int n_seq, int ctx, int heads, int width, leaf_stream_t s) {
     if (!qkv || !dout16 || !dqkv16 || n_seq < 1) { leaf_set_error("null/invalid argument"); return 1; }

@@ -86,20 +86,29 @@ extern "C" size_t leaf_text_stash_bytes(leaf_text_t h, int n_seq) {
     return align_up(c.off, 256) + 256;
 }
 
-// pool_last: pool at the last kept row of each sequence instead of the first maximum token id (leaf_text_forward_train_last)
-static int forward_train_impl(leaf_text_t h, const float* P, const void* w16_fwd, const int32_t* tokens, const int32_t* seq_lens,
-                              const int32_t* cu_rows, int n_seq, const float* delta, float* out, void* stash, size_t stash_bytes,
-                              void* ws, size_t ws_bytes, leaf_stream_t s_, bool pool_last) {
-    if (!h || !P || !w16_fwd || !tokens || !out || !stash || n_seq < 1) { leaf_set_error("null/invalid argument"); return 1; }
-    hipStream_t s = (hipStream_t)s_;
+// Training forward (include/leaf_hip.h, leaf_train_fwd_args).  pool_last: pool at the last kept row of each sequence instead of the
+// first maximum token id.  Every refusal comes before the first HIP call.
+extern "C" int leaf_text_forward_train(leaf_text_t h, const leaf_train_fwd_args* a) {
+    if (!a || a->size != sizeof(*a)) { leaf_set_error("leaf_train_fwd_args: size %u, this library's is %zu", a ? a->size : 0u, sizeof(*a)); return 1; }
+    const float* P = a->params;
+    const int32_t *tokens = a->tokens, *seq_lens = a->seq_lens, *cu_rows = a->cu_rows;
+    const float* delta = a->delta;
+    float* out = a->out;
+    void* ws = a->ws;
+    const size_t ws_bytes = a->ws_bytes;
+    const int n_seq = a->n_seq;
+    const bool pool_last = a->pool_last != 0;
+    if (!h || !P || !a->w16_fwd || !tokens || !out || !a->stash || n_seq < 1) { leaf_set_error("null/invalid argument"); return 1; }
+    hipStream_t s = (hipStream_t)a->stream;
     if ((seq_lens == nullptr) != (cu_rows == nullptr)) { leaf_set_error("seq_lens (host) and cu_rows (device) go together"); return 1; }
+    if (pool_last && delta) { leaf_set_error("forward_train: pool_last takes no delta"); return 1; }
     if (pool_last && (!seq_lens || !ws || ws_bytes < (size_t)n_seq * h->cfg.width * 4)) {
-        leaf_set_error("forward_train_last needs explicit seq_lens / cu_rows and a workspace of n_seq x width floats");
+        leaf_set_error("forward_train: pool_last needs explicit seq_lens / cu_rows and a workspace of n_seq x width floats");
         return 1;
     }
     const leaf_text_cfg& cf = h->cfg;
     const int rows = (int)total_rows(h, seq_lens, n_seq);
-    Carver c(stash, stash_bytes);
+    Carver c(a->stash, a->stash_bytes);
     Stash st = carve_stash(h, c, n_seq, rows);
     if (!c.ok()) { leaf_set_error("stash too small: need %zu bytes, have %zu", c.off, c.cap); return 1; }
     const RowMap map{cu_rows, 0, 0, cf.context_length, nullptr, nullptr, 1};
@@ -107,7 +116,7 @@ static int forward_train_impl(leaf_text_t h, const float* P, const void* w16_fwd
     for (int i = 0; i < n_seq; ++i) { const int Ls = seq_lens ? seq_lens[i] : cf.context_length; max_len = Ls > max_len ? Ls : max_len; }
     const int d = cf.width, dt = h->fwd_dtype, L = cf.layers;
     const size_t rd = (size_t)rows * d;
-    const uint16_t* W = (const uint16_t*)w16_fwd;
+    const uint16_t* W = (const uint16_t*)a->w16_fwd;
     LEAF_TRY(leaf_launch_embed_ln(tokens, P + h->tok_emb, P + h->pos_emb, P + h->layer[0].ln1_w, P + h->layer[0].ln1_b,
                                   cf.ln_eps, st.xin, st.xn1, rows, n_seq, map, d, cf.vocab_size, dt, s, delta));
     for (int l = 0; l < L; ++l) {
@@ -153,54 +162,38 @@ static int forward_train_impl(leaf_text_t h, const float* P, const void* w16_fwd
     return 0;
 }
 
-extern "C" int leaf_text_forward_train_delta(leaf_text_t h, const float* P, const void* w16_fwd, const int32_t* tokens,
-                                             const int32_t* seq_lens, const int32_t* cu_rows, int n_seq,
-                                             const float* delta, float* out, void* stash, size_t stash_bytes, void* ws,
-                                             size_t ws_bytes, leaf_stream_t s_) {
-    return forward_train_impl(h, P, w16_fwd, tokens, seq_lens, cu_rows, n_seq, delta, out, stash, stash_bytes, ws, ws_bytes, s_, false);
-}
-
-extern "C" int leaf_text_forward_train_last(leaf_text_t h, const float* P, const void* w16_fwd, const int32_t* tokens,
-                                            const int32_t* seq_lens, const int32_t* cu_rows, int n_seq, float* out, void* stash,
-                                            size_t stash_bytes, void* ws, size_t ws_bytes, leaf_stream_t s_) {
-    return forward_train_impl(h, P, w16_fwd, tokens, seq_lens, cu_rows, n_seq, nullptr, out, stash, stash_bytes, ws, ws_bytes, s_, true);
-}
-
-extern "C" int leaf_text_forward_train(leaf_text_t h, const float* P, const void* w16_fwd, const int32_t* tokens,
-                                       const int32_t* seq_lens, const int32_t* cu_rows, int n_seq, float* out,
-                                       void* stash, size_t stash_bytes, void* ws, size_t ws_bytes, leaf_stream_t s_) {
-    return leaf_text_forward_train_delta(h, P, w16_fwd, tokens, seq_lens, cu_rows, n_seq, nullptr, out, stash, stash_bytes,
-                                         ws, ws_bytes, s_);
-}
-
-// The loss whose gradient the backward starts from: TextFARE against an anchor (ref = anchor, scale = accum_scale, out = the
-// loss, one float), the cosine head of text embedding inversion (ref = target, scale = loss_weight, out = cos [n_seq]) or a loss
-// the caller computed itself (ref = dfeat = its d loss / d feat, scale = a factor on it, out unused).
-enum HeadKind { HEAD_FARE, HEAD_COSINE, HEAD_UPSTREAM };
-struct LossHead {
-    HeadKind kind;
-    const float* ref;
-    float scale;
-    float* out;
-};
-
-// Shared body of the parameter-gradient backward (G != null) and of the input-gradient-only backward of the optional
-// embedding-space PGD mode (G == null, d_embed != null: no weight / bias / LayerNorm / embedding-table gradients).
-static int backward_impl(leaf_text_t h, const float* P, const void* w16_bwd, const int32_t* tokens,
-                         const int32_t* seq_lens, const int32_t* cu_rows, int n_seq, const float* feat,
-                         const LossHead& head, const void* stash, float* G, float* d_embed, void* ws, size_t ws_bytes,
-                         leaf_stream_t s_, void* const* layer_events = nullptr) {
-    if (!h || !P || !w16_bwd || !tokens || !feat || !head.ref || !stash || (!G && !d_embed) || !ws || n_seq < 1) {
+// The backward through the stash (include/leaf_hip.h, leaf_backward_args) from the loss head a->head: TextFARE against an anchor (ref
+// = anchor, scale = accum_scale, head_out = the loss, one float), the cosine head of text embedding inversion (ref = target, scale =
+// loss_weight, head_out = cos [n_seq]) or a loss the caller computed itself (ref = dfeat = its d loss / d feat, scale = a factor on
+// it).  One body for the parameter-gradient backward (G != null) and the input-gradient-only backward of the optional embedding-space
+// PGD mode (G == null, d_embed != null: no weight / bias / LayerNorm / embedding-table gradients).  Every refusal comes before the
+// first HIP call.
+extern "C" int leaf_text_backward(leaf_text_t h, const leaf_backward_args* a) {
+    if (!a || a->size != sizeof(*a)) { leaf_set_error("leaf_backward_args: size %u, this library's is %zu", a ? a->size : 0u, sizeof(*a)); return 1; }
+    const float *P = a->params, *feat = a->feat;
+    const int32_t *tokens = a->tokens, *seq_lens = a->seq_lens, *cu_rows = a->cu_rows;
+    const int n_seq = a->n_seq, head = a->head;
+    float *G = a->grads, *d_embed = a->d_embed;
+    void* const* layer_events = a->layer_events;
+    if (!h || !P || !a->w16_bwd || !tokens || !feat || !a->ref || !a->stash || (!G && !d_embed) || !a->ws || n_seq < 1) {
         leaf_set_error("null/invalid argument");
         return 1;
     }
-    hipStream_t s = (hipStream_t)s_;
+    const bool outputs_ok = head == LEAF_HEAD_FARE     ? (G != nullptr) != (d_embed != nullptr) && (G || a->scale == 1.0f)
+                          : head == LEAF_HEAD_COSINE   ? !G
+                          : head == LEAF_HEAD_UPSTREAM;     // grads, d_embed or both
+    if (!outputs_ok) {
+        leaf_set_error("backward: head %d takes -- FARE: grads, or d_embed with scale 1; COSINE: d_embed only; UPSTREAM: either or both", head);
+        return 1;
+    }
+    if (head == LEAF_HEAD_COSINE && h->normalize_fare) { leaf_set_error("backward: the cosine head needs option normalize_fare off"); return 1; }
+    hipStream_t s = (hipStream_t)a->stream;
     if ((seq_lens == nullptr) != (cu_rows == nullptr)) { leaf_set_error("seq_lens (host) and cu_rows (device) go together"); return 1; }
     const leaf_text_cfg& cf = h->cfg;
     const int rows = (int)total_rows(h, seq_lens, n_seq);
-    Carver cs((void*)stash, (size_t)-1);
+    Carver cs((void*)a->stash, (size_t)-1);
     Stash st = carve_stash(h, cs, n_seq, rows);
-    Carver cw(ws, ws_bytes);
+    Carver cw(a->ws, a->ws_bytes);
     BwdBuf b = carve_bwd(h, cw, n_seq, rows);
     if (!cw.ok()) { leaf_set_error("workspace too small: need %zu bytes, have %zu", cw.off, cw.cap); return 1; }
     const RowMap map{cu_rows, 0, 0, cf.context_length, nullptr, nullptr, 1};
@@ -209,15 +202,15 @@ static int backward_impl(leaf_text_t h, const float* P, const void* w16_bwd, con
     const int fk = h->fwd_dtype == LEAF_DTYPE_FP16 ? 1 : 0;  // source kind of stashed activations
     const int gk = h->grad_dtype == LEAF_DTYPE_FP16 ? 1 : 0;  // 16-bit kind of the gradient path (kind == LEAF_* dtype id)
     const float* inv_s = b.gscale + 1;
-    const uint16_t* WT = (const uint16_t*)w16_bwd;
+    const uint16_t* WT = (const uint16_t*)a->w16_bwd;
 
-    if (head.kind == HEAD_COSINE)
-        LEAF_TRY(leaf_launch_cos_loss(feat, head.ref, n_seq, D, head.scale, head.out, b.dout, b.gscale, gk == 1, s));
-    else if (head.kind == HEAD_UPSTREAM)
-        LEAF_TRY(leaf_launch_upstream_grad(head.ref, feat, n_seq, D, head.scale, b.dout, b.gscale, gk == 1, s,
+    if (head == LEAF_HEAD_COSINE)
+        LEAF_TRY(leaf_launch_cos_loss(feat, a->ref, n_seq, D, a->scale, a->head_out, b.dout, b.gscale, gk == 1, s));
+    else if (head == LEAF_HEAD_UPSTREAM)
+        LEAF_TRY(leaf_launch_upstream_grad(a->ref, feat, n_seq, D, a->scale, b.dout, b.gscale, gk == 1, s,
                                            h->normalize_fare ? st.norms : nullptr, h->scaler));
     else
-        LEAF_TRY(leaf_launch_fare_loss(feat, head.ref, n_seq, D, head.scale, head.out, b.dout, b.gscale, gk == 1, s,
+        LEAF_TRY(leaf_launch_fare_loss(feat, a->ref, n_seq, D, a->scale, a->head_out, b.dout, b.gscale, gk == 1, s,
                                        h->normalize_fare ? st.norms : nullptr, h->scaler));
     const bool sat_check = h->scaler && G && gk == 1;     // fp16 gradient path with a scaler attached (leaf_hip.h "gradient scaler")
     LEAF_TRY(hipMemsetAsync(b.dx, 0, rd * 4, s));
@@ -299,58 +292,6 @@ extern "C" int leaf_text_set_grad_scaler(leaf_text_t h, float* state) {
     return 0;
 }
 
-extern "C" int leaf_textfare_backward(leaf_text_t h, const float* P, const void* w16_bwd, const int32_t* tokens,
-                                      const int32_t* seq_lens, const int32_t* cu_rows, int n_seq, const float* feat,
-                                      const float* anchor, float accum_scale,
-                                      const void* stash, float* G, float* loss_out, void* ws, size_t ws_bytes,
-                                      leaf_stream_t s_) {
-    if (!G) { leaf_set_error("null/invalid argument"); return 1; }
-    return backward_impl(h, P, w16_bwd, tokens, seq_lens, cu_rows, n_seq, feat, LossHead{HEAD_FARE, anchor, accum_scale, loss_out}, stash, G,
-                         nullptr, ws, ws_bytes, s_);
-}
-
-// The same backward with completion events for gradient-bucket overlap: layer_events[l], l = L-1 .. 0, is recorded
-// on the stream as soon as every gradient of transformer block l is final in `grads`, layer_events[L] after the last kernel
-// (embedding tables; ln_final / text_projection gradients are written first).  NULL entries are skipped.
-extern "C" int leaf_textfare_backward_events(leaf_text_t h, const float* P, const void* w16_bwd, const int32_t* tokens,
-                                             const int32_t* seq_lens, const int32_t* cu_rows, int n_seq, const float* feat,
-                                             const float* anchor, float accum_scale, const void* stash, float* G,
-                                             float* loss_out, void* ws, size_t ws_bytes, leaf_stream_t s_,
-                                             void* const* layer_events) {
-    if (!G) { leaf_set_error("null/invalid argument"); return 1; }
-    return backward_impl(h, P, w16_bwd, tokens, seq_lens, cu_rows, n_seq, feat, LossHead{HEAD_FARE, anchor, accum_scale, loss_out}, stash, G,
-                         nullptr, ws, ws_bytes, s_, layer_events);
-}
-
-extern "C" int leaf_textfare_input_grad(leaf_text_t h, const float* P, const void* w16_bwd, const int32_t* tokens,
-                                        const int32_t* seq_lens, const int32_t* cu_rows, int n_seq, const float* feat,
-                                        const float* anchor, const void* stash, float* d_embed, float* loss_out, void* ws,
-                                        size_t ws_bytes, leaf_stream_t s_) {
-    if (!d_embed) { leaf_set_error("null/invalid argument"); return 1; }
-    return backward_impl(h, P, w16_bwd, tokens, seq_lens, cu_rows, n_seq, feat, LossHead{HEAD_FARE, anchor, 1.0f, loss_out}, stash, nullptr,
-                         d_embed, ws, ws_bytes, s_);
-}
-
-extern "C" int leaf_cosine_input_grad(leaf_text_t h, const float* P, const void* w16_bwd, const int32_t* tokens,
-                                      const int32_t* seq_lens, const int32_t* cu_rows, int n_seq, const float* feat,
-                                      const float* target, float loss_weight, const void* stash, float* d_embed, float* cos_out,
-                                      void* ws, size_t ws_bytes, leaf_stream_t s_) {
-    if (!d_embed) { leaf_set_error("null/invalid argument"); return 1; }
-    if (h && h->normalize_fare) { leaf_set_error("cosine_input_grad: option normalize_fare must be off"); return 1; }
-    return backward_impl(h, P, w16_bwd, tokens, seq_lens, cu_rows, n_seq, feat, LossHead{HEAD_COSINE, target, loss_weight, cos_out}, stash,
-                         nullptr, d_embed, ws, ws_bytes, s_);
-}
-
-// Backward from a gradient the caller computed (any loss of the features): parameter gradients, the embedding-input gradient or
-// both in one pass.  backward_impl refuses a NULL dfeat and two NULL outputs before its first HIP call.
-extern "C" int leaf_text_backward(leaf_text_t h, const float* P, const void* w16_bwd, const int32_t* tokens, const int32_t* seq_lens,
-                                  const int32_t* cu_rows, int n_seq, const float* feat, const float* dfeat, float scale,
-                                  const void* stash, float* G, float* d_embed, void* ws, size_t ws_bytes, leaf_stream_t s_,
-                                  void* const* layer_events) {
-    return backward_impl(h, P, w16_bwd, tokens, seq_lens, cu_rows, n_seq, feat, LossHead{HEAD_UPSTREAM, dfeat, scale, nullptr}, stash,
-                         G, d_embed, ws, ws_bytes, s_, layer_events);
-}
-
 // the cosine head alone (kernel hook for the tests): dout [B, D], cos_out [B]; ws = 64 + 2 B floats
 extern "C" int leaf_op_cosine_head(const float* feat, const float* target, int B, int D, float loss_weight, float* dout,
                                    float* cos_out, float* ws, leaf_stream_t s) {
@@ -358,7 +299,7 @@ extern "C" int leaf_op_cosine_head(const float* feat, const float* target, int B
     return leaf_check(leaf_launch_cos_loss(feat, target, B, D, loss_weight, cos_out, dout, ws, 0, (hipStream_t)s), "cosine_head");
 }
 
-// ---- the launchers of backward_impl one at a time, on the RowMap it builds (kernel hooks of tests/test_gpu_backward_rows.py): no
+// ---- the launchers of leaf_text_backward one at a time, on the RowMap it builds (kernel hooks of tests/test_gpu_backward_rows.py): no
 // logic of their own
 extern "C" int leaf_op_pool_project_bwd(const float* dout, const float* pooled, const float* x, const int32_t* eot_idx, const float* g,
                                         float eps, const float* proj, float* dx, float* dproj, float* dg, float* db,

@@ -653,7 +653,7 @@ hipError_t leaf_launch_iota(int32_t* out, int n, hipStream_t s) {
     return hipGetLastError();
 }
 
-// ---- operand splits of the optional higher-precision blocks (leaf_text_split_pack / option "split blocks"):
+// ---- operand splits of the optional higher-precision blocks (leaf_text_split_pack_masks / option "split blocks"):
 // a fp32 value v as hi = 16-bit(v), lo = 16-bit(v - hi); hi + lo carries ~22 significand bits.  The GEMM then multiplies
 // [x_hi | x_lo | x_hi] by [W_hi | W_hi | W_lo] over a three times longer K: the fp32 accumulator receives x_hi W_hi + x_lo W_hi +
 // x_hi W_lo (the missing x_lo W_lo is 2^-22 relative) -- the unchanged GEMM kernels, no new arithmetic.

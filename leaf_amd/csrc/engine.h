@@ -56,7 +56,7 @@ struct leaf_text {
     // Residual stream of the LN-folded forward-only passes in 16 + 8 bits (common.h resid_lo4): the 16-bit copy the next GEMM
     // multiplies anyway + a remainder byte per element (block-scaled e4m3, common.h resid_lo4) instead of an fp32 row beside that copy -- the out-projection moves 8 d bytes
     // per row instead of 12 d, c_proj 14 d instead of 18 d.  Option 'compact_resid' / LEAF_COMPACT_RESID=0: fp32 rows (also what the
-    // split blocks of leaf_text_split_pack and widths the fp32 matrix-core projection does not take run on).
+    // split blocks of leaf_text_split_pack_masks and widths the fp32 matrix-core projection does not take run on).
     int compact_resid = 1;
     size_t w16_std_elems() const { return w16_layer_elems() * cfg.layers; }
     size_t w16_fold_qkv(int l) const { return w16_std_elems() + (size_t)l * 7 * cfg.width * cfg.width; }
@@ -69,7 +69,7 @@ struct leaf_text {
     const float* fold_c_qkv(const void* w16, int l) const { return fold_aux(w16, l) + 3 * cfg.width; }
     const float* fold_s_fc(const void* w16, int l) const { return fold_aux(w16, l) + 6 * cfg.width; }
     const float* fold_c_fc(const void* w16, int l) const { return fold_aux(w16, l) + 10 * cfg.width; }
-    // ---- optional higher-precision leading blocks (leaf_text_split_pack): hi + lo operand splits for the four GEMMs of blocks
+    // ---- optional higher-precision leading blocks (leaf_text_split_pack_masks): hi + lo operand splits for the four GEMMs of blocks
     // [0, split_blocks) of the forward-only passes.  Caller-owned buffer: per block 27 d^2 16-bit elements -- QKV' [3d][3d] and
     // c_fc' [4d][3d] as [hi | hi | lo] of the gamma-scaled weights, out_proj as [hi | lo] [d][2d] (ONE launch against [A | A]:
     // GemmArgs::a_wrap), the lo half of c_proj [d][4d] (a second launch) -- then (256-B aligned) per block the fp32 row sums
@@ -77,8 +77,8 @@ struct leaf_text {
     int split_blocks = 0;
     const void* split_buf = nullptr;
     // WHICH GEMMs of those blocks run on splits: one mask per block (leaf_text_split_pack_masks), bit 0 = QKV (both operands, three
-    // passes), bit 1 = out_proj (weights, two passes), bit 2 = c_fc (both operands), bit 3 = c_proj (weights); leaf_text_split_pack =
-    // 15 for every block.  profiles/r06_precision_budget_sites.txt and the census price the choices.
+    // passes), bit 1 = out_proj (weights, two passes), bit 2 = c_fc (both operands), bit 3 = c_proj (weights).
+    // profiles/r06_precision_budget_sites.txt and the census price the choices.
     int split_mask[64] = {};
     bool split_on(int l) const { return split_buf && l < split_blocks && l < 64; }
     bool split_qkv(int l) const { return split_on(l) && (split_mask[l] & 1); }
@@ -153,7 +153,7 @@ struct KvPlan {
     uint16_t* kv_write = nullptr;       // the rows of this (single) chunk are produced INTO the cache (leaf_text_forward_kv)
     const uint16_t* kv_read = nullptr;  // prefix mode: attention reads the prefix K/V of layer l from kv_read + l * kv_stride
     size_t kv_stride = 0;
-    // fused pass (leaf_score_candidates_prefix_fused): the clean captions are the FIRST kv_self_rows rows of this chunk; the
+    // fused pass (leaf_score_pass with kv_write): the clean captions are the FIRST kv_self_rows rows of this chunk; the
     // candidates' attention reads their K/V from the chunk's own rows, and every layer's caption rows also go to kv_copy
     uint16_t* kv_copy = nullptr;
     size_t kv_self_rows = 0;

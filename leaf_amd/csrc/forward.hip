@@ -70,7 +70,7 @@ struct FwdPass {
     const int d, dt;
     // ---- modes, fixed for the pass
     const bool fold;       // option ln_fold: LayerNorm folded into the GEMM epilogues (lnfold.h), else LayerNorm kernels
-    const bool splits;     // leaf_text_split_pack: hi + lo operand splits for the masked GEMMs of the leading blocks (LN-folded only)
+    const bool splits;     // leaf_text_split_pack_masks: hi + lo operand splits for the masked GEMMs of the leading blocks (LN-folded only)
     const bool lo8;        // option compact_resid, LN-folded, width the fp32 projection takes: residual stream in 16 + 8 bits (b.x16, b.x)
     const bool edit;       // option single_edit on a packed LN-folded prefix pass with a cache to read: block 0 projects one row per sequence
     const bool trim_last;  // option last_layer_trim, rows not produced into a cache: last block on the pooled rows only

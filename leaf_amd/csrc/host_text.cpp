@@ -976,7 +976,6 @@ extern "C" int leaf_dict_create(const char* words, size_t len, leaf_dict_t* out)
 }
 
 extern "C" void leaf_dict_destroy(leaf_dict_t d) { delete d; }
-extern "C" int64_t leaf_dict_size(leaf_dict_t d) { return d ? (int64_t)d->words.size() : -1; }
 
 static int constrain_impl(leaf_dict_t d, int kind, const char* const* sentences, const int32_t* sent_len, int B,
                           const int32_t* z, const int32_t* c, int rho, const int32_t* ranges, const int32_t* ranges_off,

@@ -147,39 +147,39 @@ class _KvCache:
 
 
 class _ScoreTarget:
-    """What a scoring pass compares its candidates with, the Python side of ``ScoreTarget`` in leaf_amd/csrc/api.hip: one anchor row
-    per caption under an objective, or (``class_feat`` given) a class matrix shared by all captions with a label per caption and the
-    wanted extra outputs.  ``dense`` / ``prefix`` name the C entries of the two passes; ``bind`` makes their arguments."""
+    """What a scoring pass compares its candidates with: one anchor row per caption under an objective, or (``class_feat`` given) a
+    class matrix shared by all captions with a label per caption and the wanted extra outputs.  ``bind`` writes it into the C
+    arguments of a pass (the target fields of ``leaf_score_args``, include/leaf_hip.h)."""
 
     def __init__(self, anchor=None, objective="l2", class_feat=None, labels=None, want_pred=False, want_logits=False):
         self.anchor, self.obj = anchor, _OBJ[objective]
         self.class_feat, self.labels, self.want_pred, self.want_logits = class_feat, labels, want_pred, want_logits
         self.B = int((anchor if class_feat is None else labels).shape[0])
-        self.dense, self.prefix = (("leaf_score_candidates", "leaf_score_candidates_prefix") if class_feat is None else
-                                   ("leaf_score_candidates_cls", "leaf_score_candidates_prefix_cls"))
 
-    def bind(self, rho: int, embed_dim: int, want_features: bool, want_loss: bool):
-        """Output buffers of one pass over B * rho candidates.  Returns (the C arguments from the target to the last output, which
-        both entries of the target take in this order; what the scoring call returns)."""
+    def bind(self, a: _lib.ScoreArgs, rho: int, embed_dim: int, want_features: bool, want_loss: bool):
+        """Sets the shape, target and output fields of ``a`` for one pass over B * rho candidates, with fresh output buffers.  Returns
+        (those buffers, which must outlive the call; what the scoring call returns)."""
         B, dev = self.B, (self.anchor if self.class_feat is None else self.class_feat).device
         idx = torch.empty(B, dtype=torch.int32, device=dev)
         feat = torch.empty(B, embed_dim, dtype=torch.float32, device=dev) if want_features else None
+        a.B, a.rho, a.best_idx, a.best_feat = B, rho, _ptr(idx), _ptr(feat)
         if self.class_feat is None:
             loss = torch.empty(B, rho, dtype=torch.float32, device=dev) if want_loss else None
-            return ((_ptr(self.anchor), B, rho, self.obj, _ptr(idx), _ptr(feat), _ptr(loss)),
-                    (idx, feat, loss) if want_loss else (idx, feat))
+            a.anchor, a.objective, a.loss = _ptr(self.anchor), self.obj, _ptr(loss)
+            return (idx, feat, loss), ((idx, feat, loss) if want_loss else (idx, feat))
         n_cls = int(self.class_feat.shape[0])
         loss = torch.empty(B, rho, dtype=torch.float32, device=dev)          # always: the pass takes best_idx from it
         pred = torch.empty(B, rho, dtype=torch.int32, device=dev) if self.want_pred else None
         logits = torch.empty(B * rho, n_cls, dtype=torch.float32, device=dev) if self.want_logits else None
-        return ((_ptr(self.class_feat), n_cls, _ptr(self.labels), B, rho, _ptr(idx), _ptr(feat), _ptr(loss), _ptr(pred), _ptr(logits)),
-                (idx, feat, (loss if want_loss else None), pred, logits))
+        a.class_feat, a.C, a.labels, a.loss, a.pred, a.logits = _ptr(self.class_feat), n_cls, _ptr(self.labels), _ptr(loss), _ptr(pred), _ptr(logits)
+        return (idx, feat, loss, pred, logits), (idx, feat, (loss if want_loss else None), pred, logits)
 
 
 @dataclass(slots=True)
 class _ScorePlan:
     """What ``score_candidates_prepare`` hands to ``score_candidates_run``: everything of a prefix-reuse pass but the prefix lengths.
-    The plan keeps alive every buffer whose address ``call`` holds."""
+    ``args`` holds addresses only: the plan keeps alive every buffer behind them (``tokens``, ``cache``, ``target``, ``keep``; the
+    weights are the model's)."""
     full: np.ndarray          # host int32 [n]: the candidates' full lengths
     limit: np.ndarray         # ``_prefix_limit`` of them
     host: torch.Tensor        # pinned int32 [cu (n + 1) | prefix (n)], staged for one host-to-device copy
@@ -188,9 +188,9 @@ class _ScorePlan:
     cache: _KvCache
     single_edit: bool
     target: _ScoreTarget
-    ws: torch.Tensor
+    keep: tuple               # the pass's workspace and output buffers
     ret: tuple                # what the scoring call returns
-    call: object              # the C call: (suffix lens, cu, prefix) -> None
+    args: _lib.ScoreArgs      # the C arguments, all but seq_lens / cu_rows / prefix / stream
 
 
 def _prefix_limit(full, base_lens, rho: int) -> np.ndarray:
@@ -254,8 +254,7 @@ class LeafCLIPText:
         h = C.c_void_p()
         _lib.check(self._lib.leaf_text_create(C.byref(c), _DTYPES[dtype], C.byref(h)), "leaf_text_create")
         self._h = h
-        chunk = chunk or int(os.environ.get("LEAF_CHUNK", "4096"))   # sequences-worth of rows per pass (x 77 rows)
-        _lib.check(self._lib.leaf_text_set_chunk(h, chunk), "leaf_text_set_chunk")
+        self.set_option("chunk", chunk or int(os.environ.get("LEAF_CHUNK", "4096")))   # sequences-worth of rows per pass (x 77 rows)
         self.n_params = self._lib.leaf_text_param_count(h)
         self.n_decay = self._lib.leaf_text_decay_count(h)
         with torch.cuda.device(self.device):
@@ -626,22 +625,36 @@ class LeafCLIPText:
             raise ValueError(f"{t.shape[0]} token rows != B*rho = {B}*{rho}")
         return t
 
+    def _score_args(self, target, t, rho, want_features, want_loss, **mode):
+        """(the C arguments of a scoring pass over the candidates ``t`` against ``target``: the fields that every pass sets and
+        ``mode``, those of its row mode; the workspace and output buffers behind them, to be kept until the call has returned; what
+        the pass returns)"""
+        ws = self._workspace(1, t.shape[0])
+        params, w16 = self._weights()
+        a = _lib.ScoreArgs(params=params, w16_fwd=w16, tokens=_ptr(t), ws=_ptr(ws), ws_bytes=ws.numel(), **mode)
+        outs, ret = target.bind(a, rho, self.cfg.embed_dim, want_features, want_loss)
+        return a, (ws, *outs), ret
+
+    def _score_pass(self, a: _lib.ScoreArgs) -> int:
+        """the C call of a scoring pass on the current stream; returns 2 when the rows of a fused first stage do not fit one chunk"""
+        a.stream = self._stream()
+        rc = self._lib.leaf_score_pass(self._h, a)
+        return rc if rc == 2 and a.kv_write else _lib.check(rc, "leaf_score_pass")
+
     def _score_dense(self, target, tokens, rho, want_features, want_loss, seq_lens):
         """one pass over all kept rows of the B * rho candidates, scored against ``target``"""
         plan = self._row_plan(tokens, seq_lens)
         t = self._candidates(tokens, target.B, rho)
-        args, ret = target.bind(rho, self.cfg.embed_dim, want_features, want_loss)
-        ws = self._workspace(1, t.shape[0])
+        a, keep, ret = self._score_args(target, t, rho, want_features, want_loss, seq_lens=plan.lens_ptr, cu_rows=plan.cu_ptr)
         self.rows_scored += plan.rows(t.shape[0], self.cfg.context_length)
-        _lib.check(getattr(self._lib, target.dense)(self._h, *self._weights(), _ptr(t), plan.lens_ptr, plan.cu_ptr, *args,
-                                                    _ptr(ws), ws.numel(), self._stream()), target.dense)
+        self._score_pass(a)
         return ret
 
     def score_candidates_prepare(self, tokens, anchor, rho, objective="l2", want_features=True, want_loss=False, seq_lens=None, kv=None,
                                  single_edit: bool = False) -> _ScorePlan:
         """Everything of a prefix-reuse ``score_candidates`` call that does NOT depend on the prefix lengths: the check of the cache,
-        token / anchor placement, output buffers, the length limits, a pinned staging buffer for the row plan, the C call with its
-        arguments known by now.  The search calls this BEFORE it waits for the previous stage's winners and
+        token / anchor placement, output buffers, the length limits, a pinned staging buffer for the row plan, the C arguments
+        known by now.  The search calls this BEFORE it waits for the previous stage's winners and
         ``score_candidates_run(plan, prefix_lens)`` right after them: the device idles at that boundary for as long as the host needs
         between the two (round 4, tools/stage_hole_probe.py: 270 -> 94 us at ViT-L B = 128, 181 -> 123 us at ViT-H B = 32)."""
         return self._prepare(self._anchor_target(anchor, objective), tokens, rho, want_features, want_loss, seq_lens, kv, single_edit)
@@ -651,15 +664,9 @@ class LeafCLIPText:
         self._check_cache(kv, target.B, rho, full, single_edit)
         host = torch.zeros(2 * full.size + 1, dtype=torch.int32, pin_memory=True)      # [cu (n + 1), cu[0] = 0 | prefix (n)]
         t = self._candidates(tokens, target.B, rho)
-        args, ret = target.bind(rho, self.cfg.embed_dim, want_features, want_loss)
-        ws = self._workspace(1, full.size)
-        # the C entry; its arguments in front of and behind the three that ``score_candidates_run`` computes
-        fn, front = getattr(self._lib, target.prefix), (self._h, *self._weights(), _ptr(t))
-        back = (_ptr(kv.base_cu), _ptr(kv.buf), kv.base_rows, int(full.max()), *args, _ptr(ws), ws.numel())
-
-        def call(suf, cu, pfx):
-            _lib.check(fn(*front, suf, cu, pfx, *back, self._stream()), target.prefix)
-        return _ScorePlan(full, _prefix_limit(full, kv.lens, rho), host, t, rho, kv, bool(single_edit), target, ws, ret, call)
+        a, keep, ret = self._score_args(target, t, rho, want_features, want_loss, base_cu=_ptr(kv.base_cu), kv=_ptr(kv.buf),
+                                        base_rows=kv.base_rows, max_len=int(full.max()))
+        return _ScorePlan(full, _prefix_limit(full, kv.lens, rho), host, t, rho, kv, bool(single_edit), target, keep, ret, a)
 
     def score_candidates_run(self, plan: _ScorePlan, prefix_lens):
         """The prefix-dependent rest of ``score_candidates_prepare``: row plan (suffix rows per candidate, their running sum), one
@@ -671,8 +678,9 @@ class LeafCLIPText:
         np.cumsum(suf, out=hv[1:n + 1])
         dev = plan.host.to(self.device, non_blocking=True)
         self.rows_scored += int(hv[n])
-        self._single_edit_call(plan.single_edit, lambda: plan.call(C.c_void_p(suf.ctypes.data), _ptr(dev[:n + 1]), _ptr(dev[n + 1:])),
-                               (plan.tokens, full, pfx, cache.tokens, cache.lens, plan.rho))
+        a = plan.args
+        a.seq_lens, a.cu_rows, a.prefix = suf.ctypes.data, dev.data_ptr(), dev.data_ptr() + 4 * (n + 1)      # dev: [cu (n + 1) | prefix (n)]
+        self._single_edit_call(plan.single_edit, lambda: self._score_pass(a), (plan.tokens, full, pfx, cache.tokens, cache.lens, plan.rho))
         return plan.ret
 
     # ------------------------------------------------------------------ classification scoring (classify.hip)
@@ -692,7 +700,7 @@ class LeafCLIPText:
 
     def score_candidates_cls(self, tokens, class_features: torch.Tensor, labels, rho: int, want_features=False, want_loss=True,
                              want_pred=True, want_logits=False, seq_lens=None, prefix_lens=None, kv=None):
-        """The pass of ``score_candidates`` scored against a class matrix shared by all captions (leaf_score_candidates_cls,
+        """The pass of ``score_candidates`` scored against a class matrix shared by all captions (leaf_score_pass with a class target,
         leaf_amd/csrc/classify.hip; the objective of the reference's attack_text_charmer_classification): the candidates' features are
         L2-normalised, ``class_features`` [C, D] are unit rows (the caller normalises), ``labels`` [B] (host array or tensor) the true
         classes.  loss[b, r] = max_{c != labels[b]} logit[c] - logit[labels[b]], pred[b, r] = first arg-max of the logits.
@@ -704,7 +712,7 @@ class LeafCLIPText:
     def score_candidates_fused(self, base_tokens, base_lens, tokens, anchor: torch.Tensor, rho: int, seq_lens, prefix_lens,
                                objective: str = "l2", want_features: bool = False, want_loss: bool = False, single_edit: bool = False):
         """``encode_text_kv(base_tokens)`` and the first stage's ``score_candidates(..., prefix_lens, kv)`` in ONE pass
-        (leaf_score_candidates_prefix_fused: the B clean captions ride in the launches of their B*rho candidates).
+        (leaf_score_pass with kv_write: the B clean captions ride in the launches of their B*rho candidates).
         Returns (best_idx, best_feat or None, kv cache for the later stages[, loss [B, rho] when want_loss]), or None when
         the rows do not fit one chunk (the caller then uses the two separate calls).  Bit-identical to the separate calls.
         The pass fills cache slot 0, the one ``encode_text_kv`` fills by default: earlier caches of that slot are stale once it succeeds.
@@ -721,17 +729,13 @@ class LeafCLIPText:
         # [cu (B + n + 1) | prefix (B + n): the captions' own is 0]
         dev = torch.from_numpy(np.concatenate([cu, np.zeros(B, dtype=np.int32), pfx])).pin_memory().to(self.device, non_blocking=True)
         bt, ct = self._candidates(base_tokens, B), self._candidates(tokens, B, rho)
-        t, weights = torch.cat([bt, ct], 0), self._weights()
+        t = torch.cat([bt, ct], 0)
         kvbuf = self._kv_buffer(0, int(cu[B]))
-        args, ret = target.bind(rho, self.cfg.embed_dim, want_features, want_loss)
-        ws = self._workspace(1, B + B * rho)
-        rc = self._single_edit_call(single_edit, lambda: self._lib.leaf_score_candidates_prefix_fused(
-            self._h, *weights, _ptr(t), C.c_void_p(lens.ctypes.data), _ptr(dev[:lens.size + 1]), _ptr(dev[lens.size + 1:]),
-            max(int(full.max()), int(blens.max())), *args, _ptr(kvbuf), kvbuf.numel(), _ptr(ws), ws.numel(), self._stream()),
-            (ct, full, pfx, bt, blens, rho))
-        if rc == 2:
+        a, keep, ret = self._score_args(target, t, rho, want_features, want_loss, seq_lens=lens.ctypes.data, cu_rows=dev.data_ptr(),
+                                        prefix=dev.data_ptr() + 4 * (lens.size + 1), max_len=max(int(full.max()), int(blens.max())),
+                                        kv=_ptr(kvbuf), kv_bytes=kvbuf.numel(), kv_write=1)
+        if self._single_edit_call(single_edit, lambda: self._score_pass(a), (ct, full, pfx, bt, blens, rho)) == 2:
             return None
-        _lib.check(rc, "leaf_score_candidates_prefix_fused")
         self.rows_scored += int(cu[-1])
         # q0: without single_edit the fused launch keeps the captions' Q rows on chip, layer 0 of the cache holds K and V only
         return (*ret[:2], self._kv_cache(kvbuf, dev[:B + 1], int(cu[B]), blens, bool(single_edit), bt, 0), *ret[2:])
@@ -761,7 +765,7 @@ class LeafCLIPText:
                       pool_last: bool = False) -> torch.Tensor:
         """Training-mode forward that keeps the activation stash.  ``pool_last`` (text embedding inversion, leaf_amd/inversion.py):
         pool at row ``seq_lens[i] - 1`` and keep all ``seq_lens[i]`` rows whatever the ids are -- an inverted prompt may hold
-        EOT / SOT ids anywhere (include/leaf_hip.h, leaf_text_forward_train_last); needs ``seq_lens``, excludes ``delta``.  ``delta`` (optional embedding-space PGD mode, SURVEY 8a
+        EOT / SOT ids anywhere (include/leaf_hip.h, leaf_train_fwd_args); needs ``seq_lens``, excludes ``delta``.  ``delta`` (optional embedding-space PGD mode, SURVEY 8a
         row a12): fp32 CUDA tensor [rows, width] in the PACKED row layout of this call (``rows_of(seq_lens)`` rows; dense
         [N * ctx, width] when rows are not trimmed), added to the token embeddings.  ``normalize`` = --normalize_fare
         (utils_AT.py:319): returns F.normalize(features); the following ``backward`` differentiates through it."""
@@ -782,9 +786,11 @@ class LeafCLIPText:
         ws = self._workspace(2, n)
         if self._lib.leaf_text_get_option(self._h, b"normalize_fare") != int(bool(normalize)):
             self.set_option("normalize_fare", int(bool(normalize)))
-        entry, extra = ("leaf_text_forward_train_last", ()) if pool_last else ("leaf_text_forward_train_delta", (_ptr(delta),))
-        _lib.check(getattr(self._lib, entry)(self._h, *self._weights(), _ptr(t), plan.lens_ptr, plan.cu_ptr, n, *extra,
-                                             _ptr(out), _ptr(stash), stash.numel(), _ptr(ws), ws.numel(), self._stream()), entry)
+        params, w16 = self._weights()
+        a = _lib.TrainFwdArgs(params=params, w16_fwd=w16, tokens=_ptr(t), seq_lens=plan.lens_ptr, cu_rows=plan.cu_ptr, n_seq=n,
+                              delta=_ptr(delta), pool_last=int(bool(pool_last)), out=_ptr(out), stash=_ptr(stash),
+                              stash_bytes=stash.numel(), ws=_ptr(ws), ws_bytes=ws.numel(), stream=self._stream())
+        _lib.check(self._lib.leaf_text_forward_train(self._h, a), "leaf_text_forward_train")
         self.stash_ticket += 1
         self.train_pass = _TrainPass(t, plan, n, rows, bool(normalize), bool(pool_last), self.stash_ticket)
         return out
@@ -799,20 +805,25 @@ class LeafCLIPText:
                                "overwritten the activations of this forward; one differentiable forward may be pending per model")
         return p
 
-    def _backward_call(self, p: _TrainPass, entry: str, feat: torch.Tensor, head, outs, d_embed: bool = False, events=None):
-        """The backward through the stash of pass ``p`` under one loss head.  Every C ``entry`` takes the shared arguments (handle, weights,
-        tokens, row plan, n, feat), the head's own values ``head``, the stash, its outputs ``outs(g)`` (tensors or None in the entry's
-        order; ``g``: the gradient of the token embeddings, fp32 [rows, width] packed, allocated here when ``d_embed``), workspace and
-        stream; an entry that takes block events gets ``events`` = (the caller's ``layer_events``,) behind them.  Returns ``g``."""
+    def _backward_call(self, p: _TrainPass, head: int, feat: torch.Tensor, ref: torch.Tensor, scale: float = 1.0, head_out=None,
+                       grads=None, d_embed: bool = False, layer_events=None):
+        """The backward through the stash of pass ``p`` from loss head ``head`` (``_lib.HEAD_*``; ``ref`` / ``scale`` / ``head_out``
+        as in include/leaf_hip.h, leaf_backward_args).  ``grads``: the flat buffer the parameter gradients are added to, or None;
+        ``d_embed``: also return the gradient of the token embeddings, fp32 [rows, width] packed, allocated here (else None);
+        ``layer_events``: the caller's block events or None."""
         g = torch.empty(p.rows, self.cfg.width, dtype=torch.float32, device=self.device) if d_embed else None
-        if events is not None and events[0] is not None:
-            if len(events[0]) != self.cfg.layers + 1:
+        events = None
+        if layer_events is not None:
+            if len(layer_events) != self.cfg.layers + 1:
                 raise ValueError(f"layer_events must hold {self.cfg.layers + 1} events")
-            events = ((C.c_void_p * len(events[0]))(*[C.c_void_p(e.cuda_event) for e in events[0]]),)
+            events = (C.c_void_p * len(layer_events))(*[C.c_void_p(e.cuda_event) for e in layer_events])
         ws = self._workspace(2, p.n)
-        _lib.check(getattr(self._lib, entry)(self._h, _ptr(self.flat), _ptr(self.w16_bwd), _ptr(p.tokens), p.plan.lens_ptr, p.plan.cu_ptr,
-                                             p.n, _ptr(feat), *head, _ptr(self._buf["stash"]), *map(_ptr, outs(g)), _ptr(ws), ws.numel(),
-                                             self._stream(), *(events or ())), entry)
+        a = _lib.BackwardArgs(params=_ptr(self.flat), w16_bwd=_ptr(self.w16_bwd), tokens=_ptr(p.tokens), seq_lens=p.plan.lens_ptr,
+                              cu_rows=p.plan.cu_ptr, n_seq=p.n, feat=_ptr(feat), head=head, ref=_ptr(ref), scale=float(scale),
+                              head_out=_ptr(head_out), stash=_ptr(self._buf["stash"]), grads=_ptr(grads), d_embed=_ptr(g),
+                              layer_events=C.addressof(events) if events is not None else None, ws=_ptr(ws), ws_bytes=ws.numel(),
+                              stream=self._stream())
+        _lib.check(self._lib.leaf_text_backward(self._h, a), "leaf_text_backward")
         return g
 
     def input_grad(self, feat: torch.Tensor, anchor: torch.Tensor):
@@ -822,7 +833,7 @@ class LeafCLIPText:
         p = self._last_pass("input_grad")
         loss = torch.empty((), dtype=torch.float32, device=self.device)
         anchor = anchor.to(device=self.device, dtype=torch.float32).contiguous()
-        return loss, self._backward_call(p, "leaf_textfare_input_grad", feat.contiguous(), (_ptr(anchor),), lambda g: (g, loss), d_embed=True)
+        return loss, self._backward_call(p, _lib.HEAD_FARE, feat.contiguous(), anchor, head_out=loss, d_embed=True)
 
     def cosine_input_grad(self, feat: torch.Tensor, target: torch.Tensor, loss_weight: float = 1.0):
         """Cosine head of text embedding inversion on the stash of the last ``forward_train``: per sequence b the loss
@@ -834,8 +845,7 @@ class LeafCLIPText:
         if tuple(target.shape) != (p.n, self.cfg.embed_dim) or tuple(feat.shape) != (p.n, self.cfg.embed_dim):
             raise ValueError(f"feat and target must be [{p.n}, {self.cfg.embed_dim}]")
         cos = torch.empty(p.n, dtype=torch.float32, device=self.device)
-        return cos, self._backward_call(p, "leaf_cosine_input_grad", feat.contiguous(), (_ptr(target), float(loss_weight)),
-                                        lambda g: (g, cos), d_embed=True)
+        return cos, self._backward_call(p, _lib.HEAD_COSINE, feat.contiguous(), target, loss_weight, head_out=cos, d_embed=True)
 
     def nn_project(self, embeds: torch.Tensor):
         """PEZ's projection step (nn_project, src/pez/optim_utils.py:26-55): for every row of ``embeds`` [M, width] the id of the
@@ -875,14 +885,12 @@ class LeafCLIPText:
         p = self._last_pass("backward")
         loss = torch.empty((), dtype=torch.float32, device=self.device)
         anchor = anchor.to(device=self.device, dtype=torch.float32).contiguous()
-        # the _events entry with NULL events is leaf_textfare_backward
-        self._backward_call(p, "leaf_textfare_backward_events", feat.contiguous(), (_ptr(anchor), float(accum_scale)),
-                            lambda g: (self.grads, loss), events=(layer_events,))
+        self._backward_call(p, _lib.HEAD_FARE, feat.contiguous(), anchor, accum_scale, head_out=loss, grads=self.grads, layer_events=layer_events)
         return loss
 
     def backward_from(self, feat: torch.Tensor, dfeat: torch.Tensor, accum_scale: float = 1.0, param_grads: bool = True,
                       want_input_grad: bool = False, layer_events=None, ticket: Optional[int] = None):
-        """Backward from ANY upstream gradient through the stash of the last ``forward_train`` (leaf_text_backward): ``dfeat``
+        """Backward from ANY upstream gradient through the stash of the last ``forward_train`` (LEAF_HEAD_UPSTREAM): ``dfeat``
         [n, embed_dim] = d loss / d ``feat`` of a loss the caller computed; ``accum_scale * dfeat`` is back-propagated, through
         F.normalize as well when that forward ran with ``normalize=True``.  ``param_grads``: ACCUMULATE the parameter gradients into
         ``self.grads`` (as ``backward``); ``want_input_grad``: also return the gradient with respect to the token embeddings
@@ -897,8 +905,8 @@ class LeafCLIPText:
             raise ValueError(f"feat and dfeat must be [{p.n}, {self.cfg.embed_dim}]")
         feat = feat.detach().to(device=self.device, dtype=torch.float32).contiguous()
         dfeat = dfeat.detach().to(device=self.device, dtype=torch.float32).contiguous()
-        return self._backward_call(p, "leaf_text_backward", feat, (_ptr(dfeat), float(accum_scale)),
-                                   lambda g: (self.grads if param_grads else None, g), d_embed=want_input_grad, events=(layer_events,))
+        return self._backward_call(p, _lib.HEAD_UPSTREAM, feat, dfeat, accum_scale, grads=self.grads if param_grads else None,
+                                   d_embed=want_input_grad, layer_events=layer_events)
 
     def encode_text_train(self, text, seq_lens=None, delta: Optional[torch.Tensor] = None, normalize: bool = False,
                           pool_last: bool = False) -> torch.Tensor:

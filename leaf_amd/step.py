@@ -231,7 +231,7 @@ def reduce_token_rows(table: torch.Tensor, my_tokens: torch.Tensor, cap: int, gr
 
 class GradReducer:
     """Data-parallel gradient mean overlapped with the backward.  The backward records one
-    event per transformer block as soon as that block's gradients are final (leaf_textfare_backward_events); the weight
+    event per transformer block as soon as that block's gradients are final (leaf_text_backward with layer_events); the weight
     buckets (runs of consecutive blocks, >= 64 MB each: bucket_plan) are all-reduced (RCCL, sum) on a side stream while the
     backward of the earlier blocks is still running; only the last bucket (embedding tables + vectors) is exposed.  Every rank issues the same collectives in the
     same order.  LEAF_DP_OVERLAP=0 (or world size 1) falls back to ONE flat all-reduce after the backward.

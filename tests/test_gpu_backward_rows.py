@@ -1,4 +1,4 @@
-"""The kernels of the training backward on the packed row map that backward_impl (leaf_amd/csrc/api_train.hip) builds, each alone
+"""The kernels of the training backward on the packed row map that leaf_text_backward (leaf_amd/csrc/api_train.hip) builds, each alone
 through its hook and against a float64 reference of the operation (tests/util.py, pinned by tests/test_backward_ref_cpu.py):
 attn_bwd_mfma_kernel (attention_bwd.hip), the projection + ln_final backward, the embedding scatter, the TextFARE loss head and the
 fp16 saturation check (train.hip).  test_layernorm_bwd (tests/test_gpu_kernels.py) holds ln_bwd_kernel to the same rules.

@@ -1,5 +1,5 @@
 """Data parallelism with TWO ranks on the one GPU of the test box (gloo transport, CUDA tensors): the bucketed, event-driven
-gradient reduction of leaf_amd.step.GradReducer (leaf_textfare_backward_events + all-reduces on a side stream while the
+gradient reduction of leaf_amd.step.GradReducer (leaf_text_backward with layer_events + all-reduces on a side stream while the
 backward of the earlier blocks still runs) against (a) the single flat all-reduce -- bit for bit -- and (b) ONE process on the
 concatenated batch ("N-GPU step == 1-GPU step on the concatenated batch").  RCCL itself needs one device per rank
 (the driver's scaling run); everything above the transport is the code exercised here."""

@@ -157,7 +157,7 @@ def test_vitl_k5_search_every_stage_rescored_by_oracle(torch_mod):
     real_fused = m.score_candidates_fused
 
     def spy_fused(base_tokens, base_lens, tokens, anchor_, rho_, seq_lens, prefix_lens, objective="l2", **kw):
-        # the first stage of every edit: the clean captions' K/V pass rides in the same launches (leaf_score_candidates_prefix_fused)
+        # the first stage of every edit: the clean captions' K/V pass rides in the same launches (leaf_score_pass with kv_write)
         idx, feat, kv, loss = real_fused(base_tokens, base_lens, tokens, anchor_, rho_, seq_lens, prefix_lens, objective,
                                          want_features=True, want_loss=True)
         calls.append((tokens.detach().cpu().numpy().copy(), idx.cpu().numpy().copy(), loss.cpu().numpy().copy(),

@@ -157,7 +157,7 @@ def test_attention_bwd(env, L, H, n):
     tq = to16(qkv, "fp16", dev)
     tdo = to16(do, "bf16", dev)
     out = torch.zeros(n * L, 3 * d, dtype=torch.bfloat16, device=dev)
-    _lib.check(lib.leaf_op_attention_bwd(ptr(tq), 1, ptr(tdo), ptr(out), n, L, H, d, stream()), "attn_bwd")
+    _lib.check(lib.leaf_op_attention_bwd_t(ptr(tq), 1, ptr(tdo), ptr(out), 0, n, L, H, d, stream()), "attn_bwd")     # 0: bf16 gradients
     torch.cuda.synchronize()
     assert rel_l2(out.float().cpu().numpy(), want) < 5e-3
 

@@ -38,7 +38,7 @@ def test_synthetic_step_runs_and_selects_argmax():
 
 
 def test_overlapped_gradient_reduction_on_rccl_single_rank(tmp_path):
-    """The bucketed, event-driven gradient reduction (GradReducer: leaf_textfare_backward_events + RCCL all-reduces on a side
+    """The bucketed, event-driven gradient reduction (GradReducer: leaf_text_backward with layer_events + RCCL all-reduces on a side
     stream) rehearsed on the one GPU of this box: under torch.distributed.run with one rank and LEAF_BENCH_FORCE_DIST=1 the
     step must give the same loss trajectory as the flat all-reduce and as no process group at all (a one-rank sum is the
     identity), and bench.py must report the rank count it saw.  The N > 1 arithmetic is covered on CPU by tests/test_dp_gloo.py."""
@@ -69,7 +69,7 @@ def test_overlapped_gradient_reduction_on_rccl_single_rank(tmp_path):
 
 @pytest.mark.parametrize("name,B,rho", [("tiny-test-quickgelu", 8, 10), ("ViT-L-14-quickgelu", 6, 7)])
 def test_fused_caption_pass_is_bit_identical(name, B, rho):
-    """The clean captions' K/V pass fused into the first stage's scoring pass (leaf_score_candidates_prefix_fused) against the
+    """The clean captions' K/V pass fused into the first stage's scoring pass (leaf_score_pass with kv_write) against the
     two separate calls: same arg-max, same winning features, the same bytes in the K/V cache (GEMM rows do not depend on the
     launch they are computed in), and the later stage scores identically from either cache."""
     import torch

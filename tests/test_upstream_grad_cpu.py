@@ -17,16 +17,18 @@ def test_text_backward_and_upstream_head_refuse_bad_arguments_before_any_hip_cal
     fake = C.c_void_p(64)                      # never dereferenced on these paths
     n, ws_bytes = 2, 1 << 20
 
-    def backward(dfeat, grads, d_embed):
-        return l.leaf_text_backward(h, fake, fake, fake, None, None, n, fake, dfeat, 1.0, fake, grads, d_embed, fake, ws_bytes, None, None)
+    def backward(dfeat, grads, d_embed, handle=h, n_seq=n, seq_lens=None):
+        a = _lib.BackwardArgs(params=fake, w16_bwd=fake, tokens=fake, seq_lens=seq_lens, n_seq=n_seq, feat=fake, head=_lib.HEAD_UPSTREAM,
+                              ref=dfeat, scale=1.0, stash=fake, grads=grads, d_embed=d_embed, ws=fake, ws_bytes=ws_bytes)
+        return l.leaf_text_backward(handle, a)
     assert backward(None, fake, None) != 0 and b"null/invalid" in l.leaf_last_error()          # no upstream gradient
     assert backward(None, fake, fake) != 0 and b"null/invalid" in l.leaf_last_error()
     assert backward(fake, None, None) != 0 and b"null/invalid" in l.leaf_last_error()          # nothing to compute
-    assert l.leaf_text_backward(None, fake, fake, fake, None, None, n, fake, fake, 1.0, fake, fake, None, fake, ws_bytes, None, None) != 0
-    assert l.leaf_text_backward(h, fake, fake, fake, None, None, 0, fake, fake, 1.0, fake, fake, None, fake, ws_bytes, None, None) != 0
+    assert backward(fake, fake, None, handle=None) != 0
+    assert backward(fake, fake, None, n_seq=0) != 0
     # seq_lens (host) without cu_rows (device): refused as in every other entry point
     lens = (C.c_int32 * 2)(3, 4)
-    assert l.leaf_text_backward(h, fake, fake, fake, lens, None, n, fake, fake, 1.0, fake, fake, None, fake, ws_bytes, None, None) != 0
+    assert backward(fake, fake, None, seq_lens=C.addressof(lens)) != 0
     assert b"go together" in l.leaf_last_error()
 
     def head(dfeat, feat, norms, B, D, dout=fake, ws=fake):

@@ -43,7 +43,7 @@ def pos2(self, pos, b1):
     return orig_pos(self, pos, b1)
 S.SyntheticCandidates.stage2_positions = pos2
 lib = model._lib
-orig_c = lib.leaf_score_candidates_prefix
+orig_c = lib.leaf_score_pass      # the first scoring pass behind stage2_device is the second stage's prefix pass
 class Wrap:
     def __call__(self, *a):
         if ev and ev[-1][1] is None:
@@ -54,7 +54,7 @@ class Wrap:
         return orig_c(*a)
 class LibProxy:
     def __init__(self, l): object.__setattr__(self, "_l", l)
-    def __getattr__(self, k): return Wrap() if k == "leaf_score_candidates_prefix" else getattr(self._l, k)
+    def __getattr__(self, k): return Wrap() if k == "leaf_score_pass" else getattr(self._l, k)
 model._lib = LibProxy(lib)
 for it in range(14):
     S.search_synthetic(model, anchor, base, sc, it, base_lens=base_lens)
