@@ -103,6 +103,33 @@ int leaf_text_forward_precise(leaf_text_t h, const float* params, const int32_t*
                               const int32_t* cu_rows, int n_seq, float* out, int normalize, void* ws, size_t ws_bytes,
                               leaf_stream_t s);
 
+/* Per-token hidden states of the text tower (the reference ships its encoders as HuggingFace CLIPTextModel(WithProjection) and
+ * src/open_clip/transformer.py's text forward computes every row; eval_text_to_image.py:172-178 puts the tower into a diffusion
+ * pipeline as text_encoder / text_encoder_2, which reads last_hidden_state, hidden_states[-2] and text_embeds; utils_attacks.py:49-59
+ * reads pooler_output / text_embeds of the same call).  A plain pass that carries a list of TAPS: `layer` is HF's hidden_states index
+ * -- 0 = token + positional embedding, l = the output of block l - 1, layers = the last block's output -- final_ln != 0 applies
+ * ln_final to every row (last_hidden_state = {layers, 1}; SD 2.x / clip_skip: {layers - 1, 1}), and out (device) receives
+ * [n_seq, ctx, width] rows in fp32 (out_dtype 0) or the handle's 16-bit type (1: the round-to-nearest conversion of the fp32 value).
+ * Dense rows (seq_lens = cu_rows = NULL): all ctx rows of every sequence, which is what a pipeline that cross-attends to the padded
+ * positions needs.  Packed rows: positions >= seq_lens[i] come back ZERO.  feat (may be NULL): the usual [n_seq, embed_dim] features
+ * of the same pass, bit-identical to leaf_text_forward / _precise; without it the pass stops behind the highest tapped block.  A tap
+ * at `layers` runs the last block on all rows (option last_layer_trim does not apply to that pass).  precise != 0: the fp32-grade
+ * arithmetic of leaf_text_forward_precise (w16_fwd unused, out_dtype 0 only, ws of leaf_text_precise_workspace_bytes); else ws of
+ * leaf_text_workspace_bytes(h, n_seq, 0).  The taps write straight to the caller's buffers.  The final LayerNorm of a tap is the
+ * arithmetic of the pooled rows' LayerNorm (leaf_op_project_rows' xn_scratch) bit for bit.  `size` = sizeof(leaf_hidden_args),
+ * checked; every refusal is reported before any HIP call and names the field. */
+typedef struct leaf_hidden_tap { int32_t layer, final_ln; void* out; } leaf_hidden_tap;
+typedef struct leaf_hidden_args {
+    uint32_t size;
+    const float* params; const void* w16_fwd;                                                    /* w16_fwd unused when precise */
+    const int32_t *tokens, *seq_lens /* HOST */, *cu_rows; int32_t n_seq;
+    const leaf_hidden_tap* taps /* HOST */; int32_t n_taps, out_dtype /* 0 fp32, 1 = the handle's 16-bit type */;
+    float* feat; int32_t normalize;                    /* may be NULL: the usual [n_seq, embed_dim] features of the same pass */
+    int32_t precise;
+    void* ws; size_t ws_bytes; leaf_stream_t stream;
+} leaf_hidden_args;
+int leaf_text_forward_hidden(leaf_text_t h, const leaf_hidden_args* a);
+
 /* One search stage of attack_text_leaf (utils_attacks.py:330-348 / 368-386,393): forward of the B*rho candidates in `tokens`, a loss
  * per candidate, the best of the rho candidates of each caption into best_idx [B] (int32) and its feature row into best_feat (fp32
  * [B,embed_dim], may be NULL); loss: fp32 [B,rho].  Every argument is a named field; `size` = sizeof(leaf_score_args), checked.

@@ -46,6 +46,17 @@ class BackwardArgs(_Args):
                 ("stash", _P), ("grads", _P), ("d_embed", _P), ("layer_events", _P), ("ws", _P), ("ws_bytes", _Z), ("stream", _P)]
 
 
+class HiddenTap(C.Structure):
+    """leaf_hidden_tap: ``layer`` is HF's ``hidden_states`` index, ``out`` a device address of [n_seq, ctx, width] rows"""
+    _fields_ = [("layer", _I), ("final_ln", _I), ("out", _P)]
+
+
+class HiddenArgs(_Args):
+    _fields_ = [("size", C.c_uint32), ("params", _P), ("w16_fwd", _P), ("tokens", _P), ("seq_lens", _P), ("cu_rows", _P), ("n_seq", _I),
+                ("taps", _P), ("n_taps", _I), ("out_dtype", _I), ("feat", _P), ("normalize", _I), ("precise", _I),
+                ("ws", _P), ("ws_bytes", _Z), ("stream", _P)]
+
+
 HEAD_FARE, HEAD_COSINE, HEAD_UPSTREAM = range(3)      # LEAF_HEAD_*
 
 _SIGS = {
@@ -70,6 +81,7 @@ _SIGS = {
     "leaf_text_precise_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int]),
     "leaf_text_forward_precise": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
                                             C.c_void_p, C.c_size_t, C.c_void_p]),
+    "leaf_text_forward_hidden": (C.c_int, [C.c_void_p, C.POINTER(HiddenArgs)]),
     "leaf_score_pass": (C.c_int, [C.c_void_p, C.POINTER(ScoreArgs)]),
     "leaf_select_topk": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                    C.c_void_p]),

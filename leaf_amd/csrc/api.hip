@@ -342,6 +342,41 @@ extern "C" int leaf_text_forward(leaf_text_t h, const float* params, const void*
     return forward_all(h, params, w16_fwd, tokens, seq_lens, cu_rows, n_seq, out, normalize, c, (hipStream_t)s);
 }
 
+// ------------------------------------------------------------------ per-token hidden states (include/leaf_hip.h, leaf_hidden_args)
+// A plain pass with taps: the argument checks, then forward_all / precise_all.  Every refusal comes before the first HIP call.
+extern "C" int leaf_text_forward_hidden(leaf_text_t h, const leaf_hidden_args* a) {
+    if (!a || a->size != sizeof(*a)) { leaf_set_error("leaf_hidden_args: size %u, this library's is %zu", a ? a->size : 0u, sizeof(*a)); return 1; }
+    if (!h) { leaf_set_error("forward_hidden: null handle"); return 1; }
+    if (!a->params) { leaf_set_error("forward_hidden: params is null"); return 1; }
+    if (!a->tokens) { leaf_set_error("forward_hidden: tokens is null"); return 1; }
+    if (!a->ws) { leaf_set_error("forward_hidden: ws is null"); return 1; }
+    if (a->n_seq < 1) { leaf_set_error("forward_hidden: n_seq %d", a->n_seq); return 1; }
+    if (a->n_taps < 0 || (a->n_taps > 0 && !a->taps)) { leaf_set_error("forward_hidden: n_taps %d with taps %s", a->n_taps, a->taps ? "given" : "null"); return 1; }
+    if (a->n_taps < 1 && !a->feat) { leaf_set_error("forward_hidden: n_taps < 1 and feat is null: the pass has no output"); return 1; }
+    if (a->out_dtype != 0 && a->out_dtype != 1) { leaf_set_error("forward_hidden: out_dtype %d (0 fp32, 1 the handle's 16-bit type)", a->out_dtype); return 1; }
+    if (a->precise && a->out_dtype) { leaf_set_error("forward_hidden: precise writes fp32 rows (out_dtype 0)"); return 1; }
+    if (!a->precise && !a->w16_fwd) { leaf_set_error("forward_hidden: w16_fwd is null (only the precise pass does without it)"); return 1; }
+    if ((a->seq_lens == nullptr) != (a->cu_rows == nullptr)) { leaf_set_error("forward_hidden: seq_lens (host) and cu_rows (device) go together"); return 1; }
+    const int L = h->cfg.layers;
+    for (int i = 0; i < a->n_taps; ++i) {
+        const leaf_hidden_tap& t = a->taps[i];
+        if (!t.out) { leaf_set_error("forward_hidden: taps[%d].out is null", i); return 1; }
+        if (t.layer < 0 || t.layer > L) { leaf_set_error("forward_hidden: taps[%d].layer %d outside 0..%d", i, t.layer, L); return 1; }
+        for (int j = 0; j < i; ++j)
+            if (a->taps[j].layer == t.layer && !a->taps[j].final_ln == !t.final_ln) {
+                leaf_set_error("forward_hidden: taps[%d] and taps[%d] are both (layer %d, final_ln %d)", j, i, t.layer, t.final_ln ? 1 : 0);
+                return 1;
+            }
+    }
+    if (a->n_taps > 0 && !leaf_hidden_rows_ok(h->cfg.width)) { leaf_set_error("forward_hidden: width %d (the row kernel takes width %% 4 == 0, <= 2048)", h->cfg.width); return 1; }
+    const HiddenTaps taps{a->taps, a->n_taps, a->out_dtype};
+    const HiddenTaps* tp = a->n_taps > 0 ? &taps : nullptr;
+    hipStream_t s = (hipStream_t)a->stream;
+    if (a->precise) return precise_all(h, a->params, a->tokens, a->seq_lens, a->cu_rows, a->n_seq, a->feat, a->normalize, a->ws, a->ws_bytes, s, tp);
+    Carver c(a->ws, a->ws_bytes);
+    return forward_all(h, a->params, a->w16_fwd, a->tokens, a->seq_lens, a->cu_rows, a->n_seq, a->feat, a->normalize, c, s, PrefixPlan(), tp);
+}
+
 // ------------------------------------------------------------------ scoring passes
 namespace {
 // argument checks of the class target (loss is required: best_idx is taken from it)

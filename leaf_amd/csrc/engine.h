@@ -161,10 +161,24 @@ struct KvPlan {
     int attn_tiles = 0;
     int attn_max_len = 0;     // longest sequence (prefix + computed rows) the plan was cut for: sizes the caption images
 };
+// Hidden-state taps of a pass (leaf_text_forward_hidden): `layer` is HF's hidden_states index -- 0 = the embedding, l = the output of
+// block l - 1 -- and every tap's rows go to its out[n_seq, ctx, width] (fp32, or the handle's 16-bit type with out16), the sequences
+// of a chunk at their place in it
+struct HiddenTaps {
+    const leaf_hidden_tap* t;
+    int n, out16;
+    int top() const {     // highest tapped index: a pass without a feature output stops behind block top - 1
+        int m = -1;
+        for (int i = 0; i < n; ++i) m = t[i].layer > m ? t[i].layer : m;
+        return m;
+    }
+};
 // the layer stack on one chunk of `cs` sequences (`rows` = their packed row count); features -> out [cs, D], or out == null:
 // K/V-only pass.  max_len: longest sequence (prefix + computed rows); 0 = context_length
+// taps (may be null): hidden states for the caller; with them out == null means "no features": the pass stops behind the highest
+// tapped block
 int forward_chunk(const leaf_text* h, const float* P, const uint16_t* W, const int32_t* tokens, int cs, int rows, RowMap map,
-                  float* out, int normalize, const FwdBuf& b, hipStream_t s, const KvPlan& kv, int max_len);
+                  float* out, int normalize, const FwdBuf& b, hipStream_t s, const KvPlan& kv, int max_len, const HiddenTaps* taps = nullptr);
 
 struct PrefixPlan {   // prefix reuse: see RowMap in common.h
     const int32_t* prefix_dev = nullptr;
@@ -179,7 +193,11 @@ struct PrefixPlan {   // prefix reuse: see RowMap in common.h
 };
 // all sequences of a pass, in chunks bounded by a row budget; carves one FwdBuf per stream from `c`
 int forward_all(leaf_text* h, const float* P, const void* W, const int32_t* tokens, const int32_t* lens, const int32_t* cu_dev,
-                int n_seq, float* out, int normalize, Carver& c, hipStream_t s, const PrefixPlan& pp = PrefixPlan());
+                int n_seq, float* out, int normalize, Carver& c, hipStream_t s, const PrefixPlan& pp = PrefixPlan(),
+                const HiddenTaps* taps = nullptr);
+// the fp32-grade pass (precise.hip) over all sequences; out may be null with taps
+int precise_all(const leaf_text* h, const float* params, const int32_t* tokens, const int32_t* seq_lens, const int32_t* cu_rows, int n_seq,
+                float* out, int normalize, void* ws, size_t ws_bytes, hipStream_t s, const HiddenTaps* taps = nullptr);
 
 // operands of a block's QKV product C = A[M, K] B[3d, K]^T: the LN-folded form reads ln_s and bias = c, the plain one bias alone
 struct QkvOperands {

@@ -60,12 +60,14 @@ struct FwdPass {
     const int32_t* tokens;
     const int cs, rows;      // sequences and packed rows of the chunk
     const RowMap map;
-    float* const out;        // [cs, D] features; null = K/V-only pass: the last block stops behind its q|k|v rows
+    float* const out;        // [cs, D] features; null = K/V-only pass: the last block stops behind its q|k|v rows (a hidden pass
+                             // without features: it stops behind the highest tapped block)
     const int normalize;
     const FwdBuf b;
     const hipStream_t s;
     const KvPlan kv;
     const int max_len;
+    const HiddenTaps* const taps;   // hidden states for the caller (leaf_text_forward_hidden), or null
     const leaf_text_cfg& c;
     const int d, dt;
     // ---- modes, fixed for the pass
@@ -73,18 +75,18 @@ struct FwdPass {
     const bool splits;     // leaf_text_split_pack_masks: hi + lo operand splits for the masked GEMMs of the leading blocks (LN-folded only)
     const bool lo8;        // option compact_resid, LN-folded, width the fp32 projection takes: residual stream in 16 + 8 bits (b.x16, b.x)
     const bool edit;       // option single_edit on a packed LN-folded prefix pass with a cache to read: block 0 projects one row per sequence
-    const bool trim_last;  // option last_layer_trim, rows not produced into a cache: last block on the pooled rows only
+    const bool trim_last;  // option last_layer_trim, rows not produced into a cache or handed to the caller: last block on the pooled rows only
 
     FwdPass(const leaf_text* h_, const float* P_, const uint16_t* W_, const int32_t* tokens_, int cs_, int rows_, const RowMap& map_,
-            float* out_, int normalize_, const FwdBuf& b_, hipStream_t s_, const KvPlan& kv_, int max_len_)
+            float* out_, int normalize_, const FwdBuf& b_, hipStream_t s_, const KvPlan& kv_, int max_len_, const HiddenTaps* taps_)
         : h(h_), P(P_), W(W_), tokens(tokens_), cs(cs_), rows(rows_), map(map_), out(out_), normalize(normalize_), b(b_), s(s_), kv(kv_),
-          max_len(max_len_), c(h_->cfg), d(c.width), dt(h_->fwd_dtype),
+          max_len(max_len_), taps(taps_), c(h_->cfg), d(c.width), dt(h_->fwd_dtype),
           fold(h->ln_fold != 0),
           splits(fold && h->split_buf && h->split_blocks > 0),
           lo8(fold && h->compact_resid && leaf_project_rows_ok(d, c.embed_dim)),
           edit(h->single_edit && fold && map.cu && map.prefix && map.base_cu && c.layers > 1 && !kv.kv_write &&
                (kv.kv_read || (kv.kv_copy && kv.kv_self_rows))),
-          trim_last(h->last_trim && !kv.kv_write) {}
+          trim_last(h->last_trim && !kv.kv_write && !(taps && taps->top() == c.layers)) {}
 
     bool sq(int l) const { return splits && h->split_qkv(l); }   // block l's QKV product runs on [hi | lo | hi] rows over K = 3d
     Resid full() const { return Resid{b.x, b.x16, rows, rows}; }
@@ -315,16 +317,35 @@ struct FwdPass {
         return project(p.xg, true, p.xn);
     }
 
+    // ---- hidden states for the caller: the full rows of the stream as they stand behind `layer` blocks (HF's hidden_states index)
+    // -> every tap of that index, the chunk's sequences at their place in the tap's [n_seq, ctx, d]
+    int tap_rows(int layer) const {
+        for (int i = 0; taps && i < taps->n; ++i) {
+            const leaf_hidden_tap& t = taps->t[i];
+            if (t.layer != layer) continue;
+            char* dst = (char*)t.out + (size_t)map.s0 * c.context_length * d * (taps->out16 ? 2 : 4);
+            LEAF_TRY(leaf_launch_hidden_rows(b.x, lo8 ? b.x16 : nullptr, P + h->lnf_w, P + h->lnf_b, c.ln_eps, t.final_ln, dst, taps->out16,
+                                             cs, map, d, dt, s));
+        }
+        return 0;
+    }
+
     int run() const {
+        const bool kv_only = !out && !taps;                     // clean captions for the cache
+        const int stop = !out && taps ? taps->top() : -1;       // hidden pass without features: nothing consumes the blocks behind
         if (embed()) return 1;
+        if (tap_rows(0)) return 1;
+        if (stop == 0) return 0;
         for (int l = 0; l < c.layers; ++l) {
             const LayerOff& o = h->layer[l];
             const bool last = l == c.layers - 1;
             if (l > 0 && !fold) LEAF_TRY(leaf_launch_layernorm(b.x, P + o.ln1_w, P + o.ln1_b, c.ln_eps, b.a, rows, d, dt, s));
-            if (attention_stage(l, last && trim_last, last && !out)) return 1;
-            if (last && !out) return 0;          // K/V-only pass (clean captions for the cache): nothing consumes the rest
+            if (attention_stage(l, last && trim_last, last && kv_only)) return 1;
+            if (last && kv_only) return 0;          // K/V-only pass: nothing consumes the rest
             if (last && trim_last) return pooled_tail_and_project(l);
             if (block_tail(l, full(), b.hh, !last)) return 1;      // (ln_final runs on the pooled rows)
+            if (tap_rows(l + 1)) return 1;
+            if (stop == l + 1) return 0;
         }
         return pool_and_project();
     }
@@ -358,14 +379,14 @@ int plan_attn_tiles(leaf_text* h, const int32_t* lens, int s0, int s1, const Pre
 }  // namespace
 
 int forward_chunk(const leaf_text* h, const float* P, const uint16_t* W, const int32_t* tokens, int cs, int rows, RowMap map,
-                  float* out, int normalize, const FwdBuf& b, hipStream_t s, const KvPlan& kv, int max_len) {
-    return FwdPass(h, P, W, tokens, cs, rows, map, out, normalize, b, s, kv, max_len).run();
+                  float* out, int normalize, const FwdBuf& b, hipStream_t s, const KvPlan& kv, int max_len, const HiddenTaps* taps) {
+    return FwdPass(h, P, W, tokens, cs, rows, map, out, normalize, b, s, kv, max_len, taps).run();
 }
 
 // Sequences are processed in chunks bounded by a ROW budget (chunk * ctx rows): with EOT-trimmed (packed) rows a
 // chunk holds more sequences, so the GEMMs keep their M.  lens == nullptr -> dense (every sequence ctx rows).
 int forward_all(leaf_text* h, const float* P, const void* W, const int32_t* tokens, const int32_t* lens, const int32_t* cu_dev,
-                int n_seq, float* out, int normalize, Carver& c, hipStream_t s, const PrefixPlan& pp) {
+                int n_seq, float* out, int normalize, Carver& c, hipStream_t s, const PrefixPlan& pp, const HiddenTaps* taps) {
     const int ctx = h->cfg.context_length;
     if ((lens == nullptr) != (cu_dev == nullptr)) { leaf_set_error("seq_lens (host) and cu_rows (device) go together"); return 1; }
     const size_t budget = (size_t)(n_seq < h->chunk ? n_seq : h->chunk) * ctx;
@@ -409,8 +430,8 @@ int forward_all(leaf_text* h, const float* P, const void* W, const int32_t* toke
             rows / 256 * (size_t)h->cfg.heads >= 256 &&      // at least a chip's worth of (256-row tile, head) items
             plan_attn_tiles(h, lens, s0, s1, pp, max_len, buf.tile_seq, s, kv))
             return 1;
-        if (forward_chunk(h, P, (const uint16_t*)W, tokens, s1 - s0, (int)rows, map, out + (size_t)s0 * h->cfg.embed_dim, normalize,
-                          buf, s, kv, max_len))
+        if (forward_chunk(h, P, (const uint16_t*)W, tokens, s1 - s0, (int)rows, map, out ? out + (size_t)s0 * h->cfg.embed_dim : nullptr,
+                          normalize, buf, s, kv, max_len, taps))
             return 1;
         s0 = s1;
         row0 += rows;

@@ -129,6 +129,13 @@ hipError_t leaf_launch_fold_pack(const float* qkv_w, const float* fc_w, size_t w
 bool leaf_project_rows_ok(int d, int D);
 hipError_t leaf_launch_project_rows(const float* xg, const float* g, const float* b, float eps, const float* proj,
                                     float* xn, float* out, int M, int d, int D, int normalize, hipStream_t s);
+// project.hip: per-token hidden states for the caller.  out[n_seq, ctx, d] (fp32, or with out16 the 16-bit type `dtype`) = the
+// chunk's residual rows by (sequence, position) -- x16 == null: x = fp32 rows; else x = the remainder bytes beside the 16-bit copy
+// x16 (common.h resid_decode4) -- optionally through the final LayerNorm (g, b: the arithmetic of leaf_launch_project_rows' LayerNorm,
+// bit for bit); zeros for positions a packed sequence does not keep.  d % 4 == 0, d <= 2048.
+bool leaf_hidden_rows_ok(int d);
+hipError_t leaf_launch_hidden_rows(const void* x, const void* x16, const float* g, const float* b, float eps, int final_ln, void* out,
+                                   int out16, int n_seq, RowMap map, int d, int dtype, hipStream_t s);
 hipError_t leaf_launch_pool_project(const float* x, const int32_t* tokens, const float* g, const float* b, float eps,
                                     const float* proj, float* out, float* pooled, int32_t* eot_idx, int n_seq, RowMap map,
                                     int d, int D, int normalize, hipStream_t s, int rows_are_pooled = 0);

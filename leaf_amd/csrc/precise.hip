@@ -248,13 +248,27 @@ int pgemm(int epi, const float* A, const float* W, float* C, const float* bias, 
     return leaf_check(hipGetLastError(), "precise gemm");
 }
 
+// taps (may be null): the fp32 rows b.x behind `layer` blocks for the caller, as FwdPass::tap_rows (forward.hip); with them
+// out == null = no features: the pass stops behind the highest tapped block
 int precise_chunk(const leaf_text* h, const float* P, const int32_t* tokens, int cs, int rows, RowMap map, float* out, int normalize,
-                  const PBuf& b, hipStream_t s) {
+                  const PBuf& b, hipStream_t s, const HiddenTaps* taps) {
     const leaf_text_cfg& c = h->cfg;
     const int d = c.width;
     const dim3 rgrid((rows + 3) / 4);
+    auto tap_rows = [&](int layer) {
+        for (int i = 0; taps && i < taps->n; ++i) {
+            const leaf_hidden_tap& t = taps->t[i];
+            if (t.layer != layer) continue;
+            float* dst = (float*)t.out + (size_t)map.s0 * c.context_length * d;
+            LEAF_TRY(leaf_launch_hidden_rows(b.x, nullptr, P + h->lnf_w, P + h->lnf_b, c.ln_eps, t.final_ln, dst, 0, cs, map, d, h->fwd_dtype, s));
+        }
+        return 0;
+    };
+    const int stop = !out && taps ? taps->top() : -1;
     hipLaunchKernelGGL(pembed_kernel, rgrid, dim3(256), 0, s, tokens, P + h->tok_emb, P + h->pos_emb, b.x, rows, cs, map, d, c.vocab_size);
     LEAF_TRY(hipGetLastError());
+    if (tap_rows(0)) return 1;
+    if (stop == 0) return 0;
     for (int l = 0; l < c.layers; ++l) {
         const LayerOff& o = h->layer[l];
         hipLaunchKernelGGL(pln_kernel, rgrid, dim3(256), 0, s, b.x, P + o.ln1_w, P + o.ln1_b, c.ln_eps, b.xn, rows, d);
@@ -264,6 +278,8 @@ int precise_chunk(const leaf_text* h, const float* P, const int32_t* tokens, int
         hipLaunchKernelGGL(pln_kernel, rgrid, dim3(256), 0, s, b.x, P + o.ln2_w, P + o.ln2_b, c.ln_eps, b.xn, rows, d);
         if (pgemm(1, b.xn, P + o.fc_w, b.hid, P + o.fc_b, rows, 4 * d, d, c.activation, s)) return 1;
         if (pgemm(2, b.hid, P + o.proj_w, b.x, P + o.proj_b, rows, d, 4 * d, 0, s)) return 1;
+        if (tap_rows(l + 1)) return 1;
+        if (stop == l + 1) return 0;
     }
     LEAF_TRY(hipGetLastError());
     if (!leaf_project_rows_ok(d, c.embed_dim)) {       // widths the fp32 matrix-core projection does not take (the d = 128 test config): fp32 VALU
@@ -289,8 +305,13 @@ extern "C" size_t leaf_text_precise_workspace_bytes(leaf_text_t h, int n_seq) {
 
 extern "C" int leaf_text_forward_precise(leaf_text_t h, const float* params, const int32_t* tokens, const int32_t* seq_lens,
                                          const int32_t* cu_rows, int n_seq, float* out, int normalize, void* ws, size_t ws_bytes,
-                                         leaf_stream_t s_) {
+                                         leaf_stream_t s) {
     if (!h || !params || !tokens || !out || !ws || n_seq < 1) { leaf_set_error("null/invalid argument"); return 1; }
+    return precise_all(h, params, tokens, seq_lens, cu_rows, n_seq, out, normalize, ws, ws_bytes, (hipStream_t)s);
+}
+
+int precise_all(const leaf_text* h, const float* params, const int32_t* tokens, const int32_t* seq_lens, const int32_t* cu_rows, int n_seq,
+                float* out, int normalize, void* ws, size_t ws_bytes, hipStream_t s, const HiddenTaps* taps) {
     if ((seq_lens == nullptr) != (cu_rows == nullptr)) { leaf_set_error("seq_lens (host) and cu_rows (device) go together"); return 1; }
     const leaf_text_cfg& c = h->cfg;
     const int ctx = c.context_length, d = c.width;
@@ -298,7 +319,6 @@ extern "C" int leaf_text_forward_precise(leaf_text_t h, const float* params, con
         leaf_set_error("precise forward: unsupported shape (ctx <= 96, width %% 64 == 0, width <= 2048)");
         return 1;
     }
-    hipStream_t s = (hipStream_t)s_;
     const size_t cs_max = n_seq < PRECISE_CHUNK_SEQS ? n_seq : PRECISE_CHUNK_SEQS, budget = cs_max * ctx;
     Carver cv(ws, ws_bytes);
     PBuf b;
@@ -319,7 +339,8 @@ extern "C" int leaf_text_forward_precise(leaf_text_t h, const float* params, con
             ++s1;
         }
         RowMap map{cu_rows, s0, (int)row0, ctx, nullptr, nullptr, 1, 0};
-        if (precise_chunk(h, params, tokens, s1 - s0, (int)rows, map, out + (size_t)s0 * c.embed_dim, normalize, b, s)) return 1;
+        if (precise_chunk(h, params, tokens, s1 - s0, (int)rows, map, out ? out + (size_t)s0 * c.embed_dim : nullptr, normalize, b, s, taps))
+            return 1;
         s0 = s1;
         row0 += rows;
     }

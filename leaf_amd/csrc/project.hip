@@ -8,6 +8,8 @@
 // whole projection matrix from L2 once per 8 sequences.
 //
 //   ln_rows_f32_kernel    one wave per row: two-pass mean / variance in registers, y = (x - mu) * rstd * g + b
+//   hidden_rows_kernel    the same rows for the caller: every (sequence, position) of a chunk's residual stream, optionally through
+//                         that LayerNorm (leaf_text_forward_hidden)
 //   proj_f32_kernel       tile 64 (rows) x 128 (cols), 4 waves of 32 x 64, k-step 16, register-staged double buffer
 //   l2norm_rows_kernel    F.normalize(dim=-1) for the 'sim' / 'dissim' objectives
 #include "common.h"
@@ -17,20 +19,19 @@ namespace {
 
 constexpr int MAXCH = 8;   // float4 chunks per lane -> d <= 2048
 
-__global__ __launch_bounds__(256) void ln_rows_f32_kernel(const float* __restrict__ x, const float* __restrict__ g,
-                                                          const float* __restrict__ b, float eps, float* __restrict__ y,
-                                                          int M, int d) {
-    leaf_fp16_sat_mode();
-    const int lane = threadIdx.x & 63, row = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= M) return;
-    const int nq = d >> 2;
-    const float* xi = x + (size_t)row * d;
+// LayerNorm of ONE row by a wave, the lane holding float4 chunks lane + 64 i (< nq = d / 4) in registers: `get(chunk)` delivers the
+// row, two-pass mean and variance of the centred values, `put(chunk, y)` receives y = (x - mu) * rstd * g + b.  The one statement of
+// this arithmetic for ln_rows_f32_kernel (the pooled rows in front of the projection) and hidden_rows_kernel (every row, for the
+// caller): a row's bits do not depend on which of the two normalised it.
+template <class Get, class Put>
+__device__ __forceinline__ void ln_row_f32(int lane, int nq, int d, const float* __restrict__ g, const float* __restrict__ b, float eps,
+                                           Get get, Put put) {
     float4 v[MAXCH];
     float s = 0.f;
 #pragma unroll
     for (int i = 0; i < MAXCH; ++i) {
         const int c = lane + 64 * i;
-        if (c < nq) { v[i] = *(const float4*)(xi + 4 * c); s += (v[i].x + v[i].y) + (v[i].z + v[i].w); }
+        if (c < nq) { v[i] = get(c); s += (v[i].x + v[i].y) + (v[i].z + v[i].w); }
     }
     const float mu = wave_sum(s) / (float)d;
     float q = 0.f;
@@ -48,11 +49,54 @@ __global__ __launch_bounds__(256) void ln_rows_f32_kernel(const float* __restric
         const int c = lane + 64 * i;
         if (c < nq) {
             const float4 gg = *(const float4*)(g + 4 * c), bb = *(const float4*)(b + 4 * c);
-            *(float4*)(y + (size_t)row * d + 4 * c) =
-                float4{(v[i].x - mu) * rstd * gg.x + bb.x, (v[i].y - mu) * rstd * gg.y + bb.y,
-                       (v[i].z - mu) * rstd * gg.z + bb.z, (v[i].w - mu) * rstd * gg.w + bb.w};
+            put(c, float4{(v[i].x - mu) * rstd * gg.x + bb.x, (v[i].y - mu) * rstd * gg.y + bb.y,
+                          (v[i].z - mu) * rstd * gg.z + bb.z, (v[i].w - mu) * rstd * gg.w + bb.w});
         }
     }
+}
+
+__global__ __launch_bounds__(256) void ln_rows_f32_kernel(const float* __restrict__ x, const float* __restrict__ g,
+                                                          const float* __restrict__ b, float eps, float* __restrict__ y,
+                                                          int M, int d) {
+    leaf_fp16_sat_mode();
+    const int lane = threadIdx.x & 63, row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= M) return;
+    const int nq = d >> 2;
+    const float* xi = x + (size_t)row * d;
+    float* yr = y + (size_t)row * d;
+    ln_row_f32(lane, nq, d, g, b, eps, [&](int c) { return *(const float4*)(xi + 4 * c); }, [&](int c, float4 o) { *(float4*)(yr + 4 * c) = o; });
+}
+
+// Per-token hidden states for the caller (leaf_text_forward_hidden): out[n_seq, ctx, d], one wave per OUTPUT row (sequence,
+// position), four rows per workgroup.  position < len(sequence): residual row seq_row + position of the chunk in the stream's
+// format -- an fp32 row of x, or (LO8) the pair (x16, remainder bytes x) through the resid_decode4 of the pooled-row gathers --
+// optionally through ln_row_f32 with the final LayerNorm's g, b; fp32 or (OUT16) the round-to-nearest 16-bit value of it.
+// position >= len (rows a packed pass does not compute): zeros.  No LDS, no scratch, no atomics.
+template <class TT, bool LO8, bool OUT16>
+__global__ __launch_bounds__(256) void hidden_rows_kernel(const void* __restrict__ x, const u16* __restrict__ x16,
+                                                          const float* __restrict__ g, const float* __restrict__ b, float eps,
+                                                          int final_ln, void* __restrict__ out, int n_seq, RowMap map, int d) {
+    leaf_fp16_sat_mode();
+    const int lane = threadIdx.x & 63, orow = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (orow >= n_seq * map.ctx) return;
+    const int sg = map.s0 + orow / map.ctx, pos = orow % map.ctx;
+    const int nq = d >> 2;
+    auto put = [&](int c, float4 o) {
+        const size_t at = (size_t)orow * d + 4 * c;
+        if (OUT16) *(uint2*)((u16*)out + at) = pack4<TT>(o.x, o.y, o.z, o.w);
+        else *(float4*)((float*)out + at) = o;
+    };
+    if (pos >= seq_len(map, sg)) {
+        for (int c = lane; c < nq; c += 64) put(c, float4{0.f, 0.f, 0.f, 0.f});
+        return;
+    }
+    const size_t at = (size_t)(seq_row(map, sg) + pos) * d;
+    auto get = [&](int c) {
+        if (LO8) return resid_decode4<TT>(*(const uint2*)(x16 + at + 4 * c), *(const unsigned*)((const unsigned char*)x + at + 4 * c));
+        return *(const float4*)((const float*)x + at + 4 * c);
+    };
+    if (final_ln) ln_row_f32(lane, nq, d, g, b, eps, get, put);
+    else for (int c = lane; c < nq; c += 64) put(c, get(c));
 }
 
 constexpr int BM = 64, BN = 128, BK = 16;
@@ -155,5 +199,27 @@ hipError_t leaf_launch_project_rows(const float* xg, const float* g, const float
     hipLaunchKernelGGL(ln_rows_f32_kernel, dim3((M + 3) / 4), dim3(256), 0, s, xg, g, b, eps, xn, M, d);
     hipLaunchKernelGGL(proj_f32_kernel, dim3(((M + BM - 1) / BM) * (D / BN)), dim3(256), 0, s, xn, proj, out, M, D, d);
     if (normalize) hipLaunchKernelGGL(l2norm_rows_kernel, dim3((M + 3) / 4), dim3(256), 0, s, out, M, D);
+    return hipGetLastError();
+}
+
+bool leaf_hidden_rows_ok(int d) { return d >= 4 && d % 4 == 0 && d <= 4 * 64 * MAXCH; }
+
+// out[n_seq, ctx, d] (fp32, or 16-bit of `dtype` with out16) = the chunk's residual rows by (sequence, position), zeros behind a
+// sequence's kept rows; x16 == null: x = fp32 rows, else x = the remainder bytes beside the 16-bit copy x16 (`dtype`)
+hipError_t leaf_launch_hidden_rows(const void* x, const void* x16, const float* g, const float* b, float eps, int final_ln, void* out,
+                                   int out16, int n_seq, RowMap map, int d, int dtype, hipStream_t s) {
+    if (!leaf_hidden_rows_ok(d) || n_seq < 1 || !x || !out || (final_ln && (!g || !b))) return hipErrorInvalidValue;
+    const dim3 grid((unsigned)(((size_t)n_seq * map.ctx + 3) / 4));
+#define HIDDEN_ROWS(TT, LO8, OUT16)                                                                                           \
+    hipLaunchKernelGGL((hidden_rows_kernel<TT, LO8, OUT16>), grid, dim3(256), 0, s, x, (const u16*)x16, g, b, eps, final_ln, out, n_seq, \
+                       map, d)
+#define HIDDEN_ROWS_T(TT)                                                 \
+    do {                                                                  \
+        if (x16) { if (out16) HIDDEN_ROWS(TT, true, true); else HIDDEN_ROWS(TT, true, false); }    \
+        else { if (out16) HIDDEN_ROWS(TT, false, true); else HIDDEN_ROWS(TT, false, false); }      \
+    } while (0)
+    if (dtype == LEAF_F16) HIDDEN_ROWS_T(F16); else HIDDEN_ROWS_T(BF16);
+#undef HIDDEN_ROWS_T
+#undef HIDDEN_ROWS
     return hipGetLastError();
 }

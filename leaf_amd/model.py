@@ -5,6 +5,7 @@ group first) plus 16-bit MFMA operand copies, and exposes
 
 * ``encode_text(text, normalize=False)``   -- src/open_clip/model.py:269-284
 * ``score_candidates(tokens, anchor, rho, objective)`` -- one stage of utils_attacks.py:297-393
+* ``encode_text_hidden(text, layers, final_ln)``     -- per-token hidden states in HF's ``hidden_states`` index (leaf_amd/hf_text.py)
 * ``forward_train`` / ``backward`` / ``adamw_step``    -- utils_AT.py:317-362
 * ``encode_text_train`` / ``backward_from``            -- the same forward under autograd: any PyTorch loss of the features
 * ``state_dict`` / ``load_state_dict`` with OpenCLIP keys and HF ``CLIPTextModel`` keys
@@ -547,6 +548,64 @@ class LeafCLIPText:
         _lib.check(getattr(self._lib, entry)(self._h, *weights, _ptr(t), plan.lens_ptr, plan.cu_ptr, n, _ptr(out), int(bool(normalize)),
                                              _ptr(ws), ws.numel(), self._stream()), entry)
         return out
+
+    def hidden_taps(self, layers=(-1,), final_ln=True):
+        """[(layer, final_ln)] of ``encode_text_hidden``'s arguments, ``layer`` in HF's ``hidden_states`` index 0..cfg.layers: negative
+        indices count from the end of that tuple (-1 = cfg.layers, -2 = cfg.layers - 1); ``final_ln`` a bool or one per layer."""
+        layers = [int(l) for l in layers]
+        lns = [bool(final_ln)] * len(layers) if isinstance(final_ln, (bool, int)) else [bool(x) for x in final_ln]
+        if len(lns) != len(layers):
+            raise ValueError(f"final_ln: {len(lns)} values for {len(layers)} layers")
+        n = self.cfg.layers + 1
+        if any(l < -n or l >= n for l in layers):
+            raise ValueError(f"layers {layers}: hidden_states has {n} entries (0 = embedding .. {n - 1} = last block)")
+        return [(l + n if l < 0 else l, ln) for l, ln in zip(layers, lns)]
+
+    def encode_text_hidden(self, text, layers=(-1,), final_ln=True, seq_lens="dense", precise: Optional[bool] = None,
+                           dtype: torch.dtype = torch.float32, want_features: bool = False, normalize: bool = False):
+        """Per-token hidden states (include/leaf_hip.h, leaf_text_forward_hidden): a list with one ``[N, ctx, width]`` tensor per
+        entry of ``layers``, in HF ``CLIPTextModel``'s ``hidden_states`` index (0 = token + positional embedding, l = output of block
+        l - 1; negative indices from the end: -1 = the last block, -2 = the one before).  ``final_ln`` (a bool, or one per layer)
+        applies ``ln_final`` to every row: ``last_hidden_state`` is ``layers=(-1,), final_ln=True`` (SD 1.x), SDXL's
+        ``hidden_states[-2]`` is ``layers=(-2,), final_ln=False``, SD 2.x / clip_skip is ``(-2,)`` with ``final_ln=True``.
+        ``dtype``: ``torch.float32`` or the model's 16-bit type (the rounded fp32 value).  ``want_features``: also return the
+        ``[N, embed_dim]`` features of the same pass (``encode_text``'s bits): ``(states, features)``.
+
+        ROWS.  ``seq_lens="dense"`` (the default) computes all ctx rows of every sequence, whatever the tokens' device: a diffusion
+        pipeline cross-attends to the padded positions too (HF pads with the EOT id), so the rows behind the EOT are part of the
+        result.  EOT trimming is OPT-IN here, unlike in ``encode_text``: ``seq_lens=None`` (lengths from host-resident tokens, as
+        ``encode_text``; device-resident tokens still run dense) or an array of lengths runs packed rows, and every row at a position
+        >= the sequence's length comes back ZERO.  Rows in front of the EOT are bit-identical either way.
+        ``precise``: as ``encode_text`` (fp32 states only)."""
+        taps = self.hidden_taps(layers, final_ln)
+        if precise is None:
+            precise = self.precise_encode
+        half = torch.float16 if self.dtype_name == "fp16" else torch.bfloat16
+        if dtype not in (torch.float32, half):
+            raise ValueError(f"dtype {dtype}: torch.float32 or the model's 16-bit type {half}")
+        if precise and dtype != torch.float32:
+            raise ValueError("precise=True returns fp32 states")
+        cfg = self.cfg
+        n = len(text)
+        with torch.cuda.device(self.device):
+            outs = [torch.empty(n, cfg.context_length, cfg.width, dtype=dtype, device=self.device) for _ in taps]
+            feat = torch.empty(n, cfg.embed_dim, dtype=torch.float32, device=self.device) if want_features else None
+        if n == 0:
+            return (outs, feat) if want_features else outs
+        plan = _RowPlan() if isinstance(seq_lens, str) and seq_lens == "dense" else self._row_plan(text, seq_lens)
+        t = self._tokens(text)
+        arr = (_lib.HiddenTap * max(len(taps), 1))(*[_lib.HiddenTap(l, int(ln), o.data_ptr()) for (l, ln), o in zip(taps, outs)])
+        if precise:
+            params, w16 = _ptr(self.flat), None
+            ws = self._grow(("ws", "precise"), self._lib.leaf_text_precise_workspace_bytes(self._h, n))
+        else:
+            params, w16 = self._weights()
+            ws = self._workspace(0, n)
+        a = _lib.HiddenArgs(params=params, w16_fwd=w16, tokens=_ptr(t), seq_lens=plan.lens_ptr, cu_rows=plan.cu_ptr, n_seq=n,
+                            taps=C.addressof(arr), n_taps=len(taps), out_dtype=int(dtype != torch.float32), feat=_ptr(feat),
+                            normalize=int(bool(normalize)), precise=int(bool(precise)), ws=_ptr(ws), ws_bytes=ws.numel(), stream=self._stream())
+        _lib.check(self._lib.leaf_text_forward_hidden(self._h, a), "leaf_text_forward_hidden")
+        return (outs, feat) if want_features else outs
 
     def encode_text_kv(self, text, seq_lens=None, want_features: bool = False, slot: int = 0):
         """Forward of the clean captions that keeps every layer's q|k|v rows for prefix reuse by the search
